@@ -22,11 +22,22 @@ always computed) at 1920x1080, all inputs resident in HBM before timing.
   instead of 118 floats per Gaussian per rank at N = 8) and ``allreduce`` runs
   the plain RCCL all-reduce.  Weak scaling; value = P * N * K / max_rank(t).
 
-Extra fields: ``roofline`` for the dominant kernel (stage times from HIP
-events recorded on the launch stream inside the timed region; algorithmic
-bytes from SURVEY.md 8(d)), ``cpu_baseline`` (the fp32 CPU restatement,
+A plain run (``--gpus 1 --steps K --warmup W``) sets up, warms up, times the
+K steps and prints the result line: nothing else.  ``--dump-outputs DIR``
+adds, after the timed steps, what the last timed step returned to its caller
+as ``DIR/<name>.npy`` (dump_outputs below); the inputs are seeded, so two
+builds can be compared output for output.
+
+``--full`` adds the extra fields: ``stages_ms_per_step`` and ``roofline`` for
+the dominant kernel (stage times from HIP events recorded on the launch
+stream, the dominant stage's inside the timed region; algorithmic bytes from
+SURVEY.md 8(d)), ``distcuda2``, ``cpu_baseline`` (the fp32 CPU restatement,
 oracle/cpu_raster.cpp, on the host cores; rank 0 at N = 1 only) and
-``psnr_vs_cpu_db`` (GPU render vs the CPU restatement's render).
+``psnr_vs_cpu_db`` (GPU render vs the CPU restatement's render).  ``--no-profile``,
+``--no-knn`` and ``--no-cpu-baseline`` drop single legs of a ``--full`` run.
+The views exchange's check against the all-reduce (N > 1, or
+``--dp-exchange``) decides which exchange is timed and stays in every run
+that times an exchange.
 """
 from __future__ import annotations
 
@@ -123,20 +134,85 @@ def load_pmc(P, W, H, sh):
     return None
 
 
+DUMP_BUDGET = 60_000_000    # bytes over all files of one --dump-outputs (the limit is 64 MB)
+
+
+def dump_outputs(dirname, small, images, rows, seed=2024):
+    """Write the outputs of one step as ``dirname/<name>.npy`` (float32;
+    plain numbers, sums and sample indices float64), DUMP_BUDGET bytes at
+    the most.
+
+    ``images``: name -> [C, H, W] tensor; ``rows``: name -> [P, ...] tensor
+    (one row per Gaussian); ``small``: name -> number or tensor of a few
+    elements, written whole.  The images are written whole while they fit
+    in 3/4 of the budget, else at one seeded sample of pixels (``pixel_sample.npy``: the flat pixel indices, sorted).
+    The per-Gaussian arrays share the rest: whole if they fit, else the rows
+    of one seeded sample of Gaussians (``gaussian_sample.npy``) plus, as a
+    check on every row, each array's sum over all Gaussians in float64
+    (``<name>_sum.npy``).  The samples depend on the sizes and the seed only."""
+    os.makedirs(dirname, exist_ok=True)
+    g = torch.Generator().manual_seed(seed)
+
+    def pick(n, item_bytes, budget):
+        if n * item_bytes <= budget:
+            return None
+        k = max(0, int(budget // (item_bytes + 8)))   # + 8: a sampled item's index
+        return torch.randperm(n, generator=g)[:k].sort().values
+
+    def save(name, t, dtype=torch.float32):
+        np.save(os.path.join(dirname, name + ".npy"), t.detach().to("cpu", dtype).contiguous().numpy())
+
+    used = 0
+    for name, v in small.items():
+        if torch.is_tensor(v):
+            save(name, v)
+        else:
+            save(name, torch.tensor([v], dtype=torch.float64), torch.float64)
+        used += 64
+    if images:
+        npix = next(iter(images.values()))[0].numel()
+        idx = pick(npix, 4 * sum(t.size(0) for t in images.values()), 0.75 * DUMP_BUDGET)
+        if idx is not None:
+            save("pixel_sample", idx, torch.float64)
+            used += 8 * idx.numel()
+        for name, t in images.items():
+            t = t if idx is None else t.reshape(t.size(0), -1)[:, idx.to(t.device)]
+            save(name, t)
+            used += 4 * t.numel()
+    if rows:
+        P = next(iter(rows.values())).size(0)
+        row_bytes = 4 * sum(t[0].numel() for t in rows.values()) if P else 0
+        sums = 8 * sum(t[0].numel() for t in rows.values()) if P else 0
+        idx = pick(P, row_bytes, DUMP_BUDGET - used - sums)
+        if idx is not None:
+            save("gaussian_sample", idx, torch.float64)
+        for name, t in rows.items():
+            if idx is not None:
+                save(name + "_sum", t.double().sum(0), torch.float64)
+                t = t[idx.to(t.device)]
+            save(name, t)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the per-stage breakdown and "
+                         "rooflines, distCUDA2, the CPU baseline and the PSNR against it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                         "(rank 0; at most 64 MB, larger arrays at a fixed seeded sample)")
     ap.add_argument("--P", type=int, default=1_000_000)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--sh", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=10.0,
                     help="CPU baseline sample: repeat the CPU step until this many seconds have passed")
-    ap.add_argument("--no-profile", action="store_true", help="skip the stage timers")
-    ap.add_argument("--no-knn", action="store_true", help="skip the distCUDA2 measurement (rocprof runs)")
+    ap.add_argument("--no-profile", action="store_true", help="--full without the stage timers")
+    ap.add_argument("--no-knn", action="store_true", help="--full without the distCUDA2 measurement")
     ap.add_argument("--dp-exchange", choices=("views", "views-dense", "allreduce"), default=None,
                     help="N > 1 gradient exchange: 'views' (default: screen-space records to the "
                          "Gaussians' owners, owner-computed shards all-gathered, only rows with "
@@ -144,8 +220,14 @@ def main():
                          "same with every row moved) or 'allreduce' (59-float gradient all-reduce). "
                          "Giving it at N = 1 runs that path on one GPU.")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    # the legs only a --full run has
+    do_profile = args.full and not args.no_profile
+    do_knn = args.full and not args.no_knn
+    do_cpu = args.full and not args.no_cpu_baseline
 
-    world = int(os.environ.get("WORLD_SIZE", "1"))
+    world =int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     # rehearsal knobs for the N > 1 code path on a one-GPU box (never used by
@@ -198,20 +280,35 @@ def main():
                 tanfovy=tany, bg=bg)
     state = {}
 
-    def step():
+    def step(keep=False):
+        """One timed step.  keep: hold on to everything the step returned to
+        its caller (state["outputs"], for --dump-outputs)."""
         nr, color, radii, geom, binning, img, depth, opacity, nt = _C.rasterize_gaussians(
             bg, means, e, opac, scales, rots, 1.0, e, view, proj, praw, tanx, tany, H, W, shs, deg,
             campos, False, False)
         if vsb is not None:
-            vsb.backward((means, scales, rots, shs, deg, camd, nr, radii, geom, binning, img), gc, gd)
+            grads, tau, _ = vsb.backward((means, scales, rots, shs, deg, camd, nr, radii, geom, binning, img),
+                                         gc, gd)
             state.update(nr=nr, color=color, img=img)
+            if keep:
+                state["outputs"] = dict(
+                    small={"num_rendered": nr, "dL_dtau_view": tau},
+                    images={"color": color, "depth": depth, "opacity": opacity},
+                    rows=dict({"dL_d" + k: v for k, v in grads.items()}, radii=radii, n_touched=nt))
             return
-        _C.rasterize_gaussians_backward(
+        bwd = _C.rasterize_gaussians_backward(
             bg, means, radii, e, scales, rots, 1.0, e, view, proj, praw, tanx, tany, gc, gd, shs,
             deg, campos, geom, nr, binning, img, False, out=gbuf.views)
         if world > 1:
             allreduce_grads(gbuf)
         state.update(nr=nr, color=color, img=img)
+        if keep:
+            names = ("dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D", "dL_dsh",
+                     "dL_dscales", "dL_drotations", "dL_dtau")
+            state["outputs"] = dict(
+                small={"num_rendered": nr},
+                images={"color": color, "depth": depth, "opacity": opacity},
+                rows=dict(zip(names, bwd), radii=radii, n_touched=nt))
 
     exchange_check = None
     if vsb is not None:
@@ -264,12 +361,12 @@ def main():
         step()
     torch.cuda.synchronize()
 
-    # per-stage breakdown first, in untimed steps (HIP events around every
-    # stage: each pair serialises the stream, ~2-3 us a stage); the timed
+    # --full: per-stage breakdown first, in untimed steps (HIP events around
+    # every stage: each pair serialises the stream, ~2-3 us a stage); the timed
     # loop then brackets only the dominant stage, for the roofline's launch
     # duration measured over the timed region itself
     breakdown, dom_stage = None, None
-    if not args.no_profile:
+    if do_profile:
         with _lib.StageProfile() as bp:
             for _ in range(min(args.steps, 10)):
                 step()
@@ -284,9 +381,10 @@ def main():
     torch.cuda.synchronize()
     if prof:
         prof.__enter__()
+    last = args.steps - 1 if (args.dump_outputs and rank == 0) else -1
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
+    for i in range(args.steps):
+        step(i == last)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -298,6 +396,8 @@ def main():
         t = torch.tensor([dt], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if "outputs" in state:
+        dump_outputs(args.dump_outputs, **state.pop("outputs"))
 
     value = P * world * args.steps / dt
     label = workload_label(P, W, H, deg, world)
@@ -433,7 +533,7 @@ def main():
                     "bytes for the kernel (48N + 24 Npix + 40P), frac_incl_zero_fill adds the gradient "
                     "outputs' zero fill it also streams")
 
-    if rank == 0 and world == 1 and not args.no_knn:
+    if rank == 0 and world == 1 and do_knn:
         # simple_knn.distCUDA2 over the scene's points
         # (outside the timed region; device time per call, HIP events)
         from simple_knn._C import distCUDA2
@@ -447,7 +547,7 @@ def main():
         torch.cuda.synchronize()
         out["distcuda2"] = {"points": P, "ms_per_call": ev0.elapsed_time(ev1) / 10,
                             "points_per_s": P / (ev0.elapsed_time(ev1) / 10 * 1e-3)}
-        if not args.no_cpu_baseline:
+        if do_cpu:
             from oracle import cpu_oracle
             t0 = time.perf_counter()
             d2c = cpu_oracle.dist_knn(scene.means3D.numpy())
@@ -455,7 +555,7 @@ def main():
             out["distcuda2"]["cpu_baseline_ms"] = 1e3 * tc
             out["distcuda2"]["bitexact_vs_cpu"] = bool(np.array_equal(d2.cpu().numpy(), d2c))
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and do_cpu:
         from oracle import cpu_oracle
         threads = int(os.environ.get("OMP_NUM_THREADS", os.cpu_count() or 1))
         # bounded sample: whole fwd+bwd steps of the same workload until

@@ -17,14 +17,17 @@ as GLSL:
   discard if power > 0, alpha = min(0.99, o exp(power)), discard if
   alpha < 1/255.
 
-This test reads those files (only in the build container: skipped where
-/root/reference is absent, e.g. on the GPU box), asserts the constants
-oracle/dense.py uses, and evaluates a line-for-line numpy transcription of
-the GLSL functions -- with GLSL's column-major ``mat3`` semantics -- against
-dense.py's preprocess on every golden scene.  It pins the oracle to
-reference TEXT, not to reference output: parity with the CUDA binary stays
-"partial" (DESIGN.md section 4).
+What those files say is recorded in tests/golden/ref_shader_facts.json
+(tests/golden/make_text_fixtures.py, run against a reference checkout: which
+of the STATEMENTS below occur in each shader, whitespace removed, and the
+values of the SH_C* defines), so the test needs no reference checkout.  It
+asserts the constants oracle/dense.py uses, and evaluates a line-for-line
+numpy transcription of the GLSL functions -- with GLSL's column-major ``mat3``
+semantics -- against dense.py's preprocess on every golden scene.  It pins
+the oracle to reference TEXT, not to reference output: parity with the CUDA
+binary stays "partial" (DESIGN.md section 4).
 """
+import json
 import math
 import os
 import re
@@ -36,13 +39,31 @@ import torch
 from _util import load_scene, scene_names
 from oracle import dense
 
-SHADERS = "/root/reference/src/gui/gl_render/shaders"
-pytestmark = pytest.mark.skipif(not os.path.isdir(SHADERS), reason="reference shaders absent (GPU box)")
+FACTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_shader_facts.json")
 
-
-def _text(name):
-    with open(os.path.join(SHADERS, name)) as f:
-        return f.read()
+# the statements the oracle's constants and formulas rest on, per shader file
+STATEMENTS = {
+    "gau_vert.glsl": {
+        "limx": "floatlimx=1.3f*tan_fovx;",
+        "limy": "floatlimy=1.3f*tan_fovy;",
+        "lowpass_x": "cov[0][0]+=0.3f;",
+        "lowpass_y": "cov[1][1]+=0.3f;",
+        "M": "mat3M=S*R;",
+        "Sigma": "mat3Sigma=transpose(M)*M;",
+        "W": "mat3W=transpose(mat3(viewmatrix));",
+        "T": "mat3T=W*J;",
+        "cov": "mat3cov=transpose(T)*transpose(cov3D)*T;",
+        "conic": "conic=vec3(cov2d.z*det_inv,-cov2d.y*det_inv,cov2d.x*det_inv);",
+        # the 3-sigma quad of the viewer (the rasteriser's radius is 3 sqrt(lambda_max))
+        "quad": "3.f*sqrt(cov2d.x)",
+    },
+    "gau_frag.glsl": {
+        "power": "floatpower=-0.5f*(conic.x*coordxy.x*coordxy.x+conic.z*coordxy.y*coordxy.y)-conic.y*coordxy.x*coordxy.y;",
+        "discard_power": "if(power>0.f)discard;",
+        "alpha": "floatopacity=min(0.99f,alpha*exp(power));",
+        "discard_alpha": "if(opacity<1.f/255.f)discard;",
+    },
+}
 
 
 def _nows(s):
@@ -110,21 +131,15 @@ def frag_alpha(conic, dx, dy, opacity):
 
 # ---- the constants ---------------------------------------------------------------
 def test_shader_constants_are_the_oracles():
-    v, f = _nows(_text("gau_vert.glsl")), _nows(_text("gau_frag.glsl"))
-    assert "floatlimx=1.3f*tan_fovx;" in v and "floatlimy=1.3f*tan_fovy;" in v
-    assert "cov[0][0]+=0.3f;" in v and "cov[1][1]+=0.3f;" in v
-    assert "mat3M=S*R;" in v and "mat3Sigma=transpose(M)*M;" in v
-    assert "mat3W=transpose(mat3(viewmatrix));" in v and "mat3T=W*J;" in v
-    assert "mat3cov=transpose(T)*transpose(cov3D)*T;" in v
-    assert "conic=vec3(cov2d.z*det_inv,-cov2d.y*det_inv,cov2d.x*det_inv);" in v
-    assert "floatpower=-0.5f*(conic.x*coordxy.x*coordxy.x+conic.z*coordxy.y*coordxy.y)-conic.y*coordxy.x*coordxy.y;" in f
-    assert "if(power>0.f)discard;" in f
-    assert "floatopacity=min(0.99f,alpha*exp(power));" in f
-    assert "if(opacity<1.f/255.f)discard;" in f
-    # the 3-sigma quad of the viewer (the rasteriser's radius is 3 sqrt(lambda_max))
-    assert "3.f*sqrt(cov2d.x)" in v
+    with open(FACTS) as fh:
+        facts = json.load(fh)
+    # every statement above was looked for in its shader, and found
+    for name, wanted in STATEMENTS.items():
+        found = facts["statements"][name]
+        assert set(found) == set(wanted), name
+        assert all(found.values()), (name, [k for k, ok in found.items() if not ok])
     # SH basis: every #define equals the oracle's constant
-    defs = dict(re.findall(r"#define\s+(SH_C\d(?:_\d)?)\s+(-?[0-9.]+)f", _text("gau_vert.glsl")))
+    defs = facts["defines"]
     assert float(defs["SH_C0"]) == dense.SH_C0 and float(defs["SH_C1"]) == dense.SH_C1
     for i in range(5):
         assert float(defs[f"SH_C2_{i}"]) == dense.SH_C2[i]

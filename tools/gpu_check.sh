@@ -23,7 +23,7 @@ for s in $STEPS; do
       fi
       if [ $rc -ge 2 ] && [ $rc -le 5 ]; then rc=0; fi ;;  # pytest usage/collection codes are not GPU faults
     bench)
-      timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > $OUT/bench${SFX:-}.json 2> $OUT/bench${SFX:-}.err; rc=$? ;;
+      timeout -k 10 600 python bench.py --full ${BENCH_ARGS:-} > $OUT/bench${SFX:-}.json 2> $OUT/bench${SFX:-}.err; rc=$? ;;
     prof)
       (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/$OUT/prof${SFX:-} -o run --output-format csv -- python $GRAFT_REPO_ROOT/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-profile --no-knn ${BENCH_ARGS:-} > $GRAFT_REPO_ROOT/$OUT/prof_bench${SFX:-}.json 2> $GRAFT_REPO_ROOT/$OUT/prof${SFX:-}.err); rc=$? ;;
     online)
@@ -70,7 +70,7 @@ for s in $STEPS; do
         lname=${v%%:*}; envset=""; tag=$lname
         if [ "$v" != "$lname" ]; then envset=${v#*:}; tag=${lname}_${envset//=/_}; fi
         if [ "$lname" = base ]; then lib=wildgs-slam-blackwell_amd/lib/libwgsr.so; else lib=wildgs-slam-blackwell_amd/lib/variants/$lname.so; fi
-        env WGSR_LIB=$lib $envset timeout -k 10 300 python bench.py --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/ab_${tag}${SFX:-}_$rep.json 2> $OUT/ab_${tag}${SFX:-}_$rep.err; rc=$?
+        env WGSR_LIB=$lib $envset timeout -k 10 300 python bench.py --full --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/ab_${tag}${SFX:-}_$rep.json 2> $OUT/ab_${tag}${SFX:-}_$rep.err; rc=$?
         if [ $rc -ne 0 ]; then break 2; fi
       done; done ;;
     knnab)

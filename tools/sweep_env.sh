@@ -13,7 +13,7 @@ for v in ${VALUES}; do
       -k "${TEST_FILTER:-golden or random or config1}" > $OUT/sweep_tests_$v.log 2>&1; rc=$?
   echo "tests $v rc=$rc" | tee -a $OUT/sweep.log
   case $rc in 124|134|137|139) exit $rc;; esac
-  env $envs timeout -k 10 300 python bench.py --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/sweep_bench_$v.json 2> $OUT/sweep_bench_$v.err; rc=$?
+  env $envs timeout -k 10 300 python bench.py --full --no-cpu-baseline ${BENCH_ARGS:-} > $OUT/sweep_bench_$v.json 2> $OUT/sweep_bench_$v.err; rc=$?
   echo "bench $v rc=$rc" | tee -a $OUT/sweep.log
   case $rc in 124|134|137|139) exit $rc;; esac
 done

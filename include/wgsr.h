@@ -772,6 +772,54 @@ const char* wgsr_version(void);
  * entries of every sort bin are ordered by depth after the bin sort. */
 int64_t wgsr_depth_order_offset(void);
 
+/* ---- droid_backends (src/lib/droid.cpp:254-266): the tracker-side ops that
+ * feed the mapper, and the correlation lookup (csrc/droid.hip).  poses
+ * [num, 7] = (tx, ty, tz, qx, qy, qz, qw), world to camera; disps
+ * [num, ht, wd] fp32; intrinsics [4] = (fx, fy, cx, cy); all device memory.
+ * ba, projmap and altcorr_* have no entry point yet. */
+
+/* Replaces droid_backends.frame_distance (DepthVideo.distance,
+ * depth_video.py:205-235): dist[k] = mean induced flow of frame ii[k]'s
+ * pixels seen from frame jj[k] (weight beta: full motion, 1 - beta:
+ * translation only; depths <= 0.25 do not count), or 1000 when fewer than
+ * 0.75 of the weighted terms count.  bidirectional != 0: 0.5 (d(ii, jj) +
+ * d(jj, ii)) in the same launch (the reference calls twice).  A pair with an
+ * index outside [0, num) reads nothing and gets NaN. */
+int wgsr_droid_frame_distance(const float* poses, const float* disps, const float* intrinsics, int num, int ht,
+                              int wd, const int64_t* ii, const int64_t* jj, int n, float beta, int bidirectional,
+                              float* dist, void* stream);
+/* Replaces droid_backends.depth_filter (DepthVideo.update_valid_depth_mask,
+ * depth_video.py:407-442): count[b, v, u] = how many of frame inds[b]'s
+ * neighbours ix-1, ix-2, ix-3, ix+3, ix+4, ix+5 (those inside [0, num)) see
+ * the pixel's point at a depth within thresh[b] of one of the four
+ * disparities around its projection.  Every element of count [m, ht, wd] is
+ * written (no zero fill needed); a frame index outside [0, num) reads
+ * nothing and gets NaN.  m <= 65535. */
+int wgsr_droid_depth_filter(const float* poses, const float* disps, const float* intrinsics, int num, int ht, int wd,
+                            const int64_t* inds, const float* thresh, int m, float* count, void* stream);
+/* Replaces droid_backends.iproj: points [num, ht, wd, 3] = (R(q) X_xyz +
+ * d t) / d.  num <= 65535. */
+int wgsr_droid_iproj(const float* poses, const float* disps, const float* intrinsics, int num, int ht, int wd,
+                     float* points, void* stream);
+
+/* element type of a correlation volume */
+#define WGSR_DTYPE_F32 0
+#define WGSR_DTYPE_F16 1
+/* Replaces droid_backends.corr_index_forward (CorrSampler.forward,
+ * corr.py:21-28): corr [n, 2r+1, 2r+1, h1, w1], corr[n, i, j, y, x] = the
+ * bilinear sample of the plane volume[n, y, x, :, :] (volume [n, h1, w1, h2,
+ * w2]) at (x0 + i - r, y0 + j - r), (x0, y0) = coords[n, :, y, x] (fp32);
+ * taps outside the plane are zero.  Accumulated in fp32, rounded once to the
+ * volume's type.  radius <= 6. */
+int wgsr_droid_corr_index_forward(const void* volume, const float* coords, int dtype, int n, int h1, int w1, int h2,
+                                  int w2, int radius, void* corr, void* stream);
+/* Replaces droid_backends.corr_index_backward (CorrSampler.backward,
+ * corr.py:30-36): volume_grad [n, h1, w1, h2, w2] = the adjoint of the
+ * forward applied to corr_grad (the volume's type).  Every element is
+ * written, zeros included: the caller needs no memset. */
+int wgsr_droid_corr_index_backward(const float* coords, const void* corr_grad, int dtype, int n, int h1, int w1,
+                                   int h2, int w2, int radius, void* volume_grad, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

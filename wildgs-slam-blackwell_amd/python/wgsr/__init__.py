@@ -5,5 +5,6 @@
 * ``wgsr.scene``    BASELINE.md synthetic scenes
 * ``wgsr.dp``       keyframe-view data parallelism over RCCL
 * ``wgsr.render``   the reference ``render()`` contract for a plain scene
+* ``wgsr.frontend`` frame distance / valid-depth mask / depth and pose over ``droid_backends``
 """
 __version__ = "0.1.0"

@@ -297,6 +297,18 @@ def load():
         L.wgsr_ply_pack.argtypes = [ctypes.POINTER(PlyColumnSet), c_int, c_i64, c_int, _fp, _fp]
         L.wgsr_ply_unpack.restype = c_int
         L.wgsr_ply_unpack.argtypes = [_fp, c_i64, c_int, ctypes.POINTER(PlyColumnSet), c_int, _fp]
+        # droid_backends (csrc/droid.hip)
+        L.wgsr_droid_frame_distance.restype = c_int
+        L.wgsr_droid_frame_distance.argtypes = ([_fp] * 3 + [c_int] * 3 + [_fp, _fp, c_int, ctypes.c_float, c_int]
+                                                + [_fp, _fp])
+        L.wgsr_droid_depth_filter.restype = c_int
+        L.wgsr_droid_depth_filter.argtypes = [_fp] * 3 + [c_int] * 3 + [_fp, _fp, c_int, _fp, _fp]
+        L.wgsr_droid_iproj.restype = c_int
+        L.wgsr_droid_iproj.argtypes = [_fp] * 3 + [c_int] * 3 + [_fp, _fp]
+        L.wgsr_droid_corr_index_forward.restype = c_int
+        L.wgsr_droid_corr_index_forward.argtypes = [_fp, _fp] + [c_int] * 7 + [_fp, _fp]
+        L.wgsr_droid_corr_index_backward.restype = c_int
+        L.wgsr_droid_corr_index_backward.argtypes = [_fp, _fp] + [c_int] * 7 + [_fp, _fp]
         L.wgsr_last_error.restype = ctypes.c_char_p
         L.wgsr_last_error.argtypes = []
         L.wgsr_version.restype = ctypes.c_char_p
@@ -337,6 +349,8 @@ EXPORTED_SYMBOLS = (
     "wgsr_sparse_grad_row_floats", "wgsr_sparse_mask_words", "wgsr_sparse_pack_records",
     "wgsr_sparse_summary_block_words", "wgsr_sparse_exchange_summary", "wgsr_sparse_unpack_records",
     "wgsr_sparse_fill_radius", "wgsr_sparse_pack_grads", "wgsr_sparse_unpack_grads",
+    "wgsr_droid_frame_distance", "wgsr_droid_depth_filter", "wgsr_droid_iproj",
+    "wgsr_droid_corr_index_forward", "wgsr_droid_corr_index_backward",
 )
 
 VIEW_RECORD_FLOATS = 12   # WGSR_VIEW_RECORD_FLOATS

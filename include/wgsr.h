@@ -776,7 +776,7 @@ int64_t wgsr_depth_order_offset(void);
  * feed the mapper, and the correlation lookup (csrc/droid.hip).  poses
  * [num, 7] = (tx, ty, tz, qx, qy, qz, qw), world to camera; disps
  * [num, ht, wd] fp32; intrinsics [4] = (fx, fy, cx, cy); all device memory.
- * ba, projmap and altcorr_* have no entry point yet. */
+ * projmap and altcorr_* have no entry point yet. */
 
 /* Replaces droid_backends.frame_distance (DepthVideo.distance,
  * depth_video.py:205-235): dist[k] = mean induced flow of frame ii[k]'s
@@ -819,6 +819,52 @@ int wgsr_droid_corr_index_forward(const void* volume, const float* coords, int d
  * written, zeros included: the caller needs no memset. */
 int wgsr_droid_corr_index_backward(const float* coords, const void* corr_grad, int dtype, int n, int h1, int w1,
                                    int h2, int w2, int radius, void* volume_grad, void* stream);
+
+/* ---- droid_backends.ba (csrc/droid_ba.hip): DROID-SLAM's dense bundle
+ * adjustment over n_edges edges (ii[e], jj[e]) with targets / weights
+ * [n_edges, 2, ht, wd].  Frames [t0, t1) have free poses (P = t1 - t0); the
+ * disparities of the K frames kx = sorted({t0..t1-1} u set(ii)) are variables,
+ * eta [K, ht, wd] their damping; disps_sens [num, ht, wd] (> 0: a sensor
+ * disparity).  A call makes no host round trip and no stream synchronisation
+ * and is bit-reproducible.  Its first kernel validates the indices and writes
+ * *status (device memory): 0, or WGSR_BA_BAD_* bits, and then every later
+ * kernel leaves poses and disps untouched (and dx, dz unwritten). */
+#define WGSR_BA_BAD_INDEX 1u /* an ii / jj entry outside [0, num)            */
+#define WGSR_BA_BAD_JJ 2u    /* a jj entry >= t1                             */
+#define WGSR_BA_BAD_K 4u     /* |kx| differs from K (eta's rows)             */
+/* bytes of caller-owned device scratch the two entry points below need
+ * (8-byte aligned); -1 (and wgsr_last_error) for sizes they would refuse */
+int64_t wgsr_droid_ba_workspace_bytes(int num, int ht, int wd, int n_edges, int t0, int t1, int K);
+/* Replaces droid_backends.ba (DepthVideo.ba, depth_video.py:351-373):
+ * `iterations` Gauss-Newton steps, each on the state the last one left;
+ * poses[t0:t1] and disps[kx] updated in place (motion_only: poses only;
+ * depth_only: disparities only).  dx [P, 6] and dz [K, ht * wd] (unused with
+ * motion_only) receive the last step.  The reduced system is assembled,
+ * damped (D <- D + ep + lm D), factored (Cholesky) and solved in fp64; a
+ * failed factorisation gives dx = 0.  The disparity step leaves out the term
+ * of pose t0's own update, as the reference does.  Bad sizes, null pointers
+ * or a short workspace return WGSR_EINVAL before any launch. */
+int wgsr_droid_ba(float* poses, float* disps, const float* intrinsics, const float* disps_sens,
+                  const float* targets, const float* weights, const float* eta, const int64_t* ii,
+                  const int64_t* jj, int num, int ht, int wd, int n_edges, int K, int t0, int t1, int iterations,
+                  float lm, float ep, int motion_only, int depth_only, void* workspace, int64_t workspace_bytes,
+                  float* dx, float* dz, uint32_t* status, void* stream);
+/* Measurement hook (tools/bench_droid_ba.py): events[0..4] (hipEvent_t, alive
+ * until the hook is reset with null) are recorded on the call's stream by
+ * every later wgsr_droid_ba / _system call of this thread, in each iteration:
+ * before the linearisation, before the reduced system's assembly (Schur
+ * complement), before the solve, after it, and after the back-substitution
+ * and retractions.  Not for use under stream capture. */
+void wgsr_droid_ba_stage_events(void** events);
+/* Diagnostic: one linearisation at the current state, nothing updated.  H
+ * [6P, 6P] and g [6P] (fp64) = the damped reduced system (A - S, a - s; with
+ * motion_only A, a), C and w [K, ht * wd] (fp32; not written, and may be
+ * null, with motion_only), dx [P, 6] the solve's result. */
+int wgsr_droid_ba_system(const float* poses, const float* disps, const float* intrinsics, const float* disps_sens,
+                         const float* targets, const float* weights, const float* eta, const int64_t* ii,
+                         const int64_t* jj, int num, int ht, int wd, int n_edges, int K, int t0, int t1, float lm,
+                         float ep, int motion_only, void* workspace, int64_t workspace_bytes, double* H, double* g,
+                         float* C, float* w, float* dx, uint32_t* status, void* stream);
 
 #ifdef __cplusplus
 }

@@ -3,11 +3,11 @@
 (bindings: src/lib/droid.cpp:254-266), computed by libwgsr.so's gfx950
 kernels (csrc/droid.hip, include/wgsr.h ``wgsr_droid_*``).
 
-Built: ``frame_distance``, ``depth_filter``, ``iproj``, ``corr_index_forward``,
-``corr_index_backward`` -- the reference's argument order and return shapes
-(the two lookups return one-element lists).  Not built yet: ``ba``,
-``projmap``, ``altcorr_forward``, ``altcorr_backward``; they raise
-``NotImplementedError`` naming the op, so a caller sees at once what is
+Built: ``ba`` (csrc/droid_ba.hip), ``frame_distance``, ``depth_filter``,
+``iproj``, ``corr_index_forward``, ``corr_index_backward`` -- the reference's
+argument order and return shapes (the two lookups return one-element lists).
+Not built yet: ``projmap``, ``altcorr_forward``, ``altcorr_backward``; they
+raise ``NotImplementedError`` naming the op, so a caller sees at once what is
 missing.  Launches go on torch's current stream.
 """
 from __future__ import annotations
@@ -171,15 +171,131 @@ def corr_index_backward(volume, coords, corr_grad, radius):
     return [volume_grad]
 
 
+# ---------------------------------------------------------------------------
+# bundle adjustment
+# ---------------------------------------------------------------------------
+BA_STATUS = {1: "an ii or jj entry lies outside [0, num)",      # WGSR_BA_BAD_INDEX
+             2: "a jj entry is >= t1",                          # WGSR_BA_BAD_JJ
+             4: "eta's rows do not match the frames {t0..t1-1} u set(ii)"}  # WGSR_BA_BAD_K
+
+
+def _ba_prepare(poses, disps, intrinsics, disps_sens, targets, weights, eta, ii, jj, t0, t1):
+    """The shared checks of ``ba`` and ``_ba_system``: (device, num, ht, wd,
+    n_edges, K, t0, t1, workspace, status)."""
+    tensors = dict(poses=poses, disps=disps, intrinsics=intrinsics, disps_sens=disps_sens, targets=targets,
+                   weights=weights, eta=eta, ii=ii, jj=jj)
+    _contiguous(**tensors)
+    dev = _device_of(**tensors)
+    num, ht, wd = _frames(poses, disps, intrinsics)
+    _index("ii", ii)
+    _index("jj", jj)
+    n = ii.numel()
+    if jj.numel() != n:
+        raise RuntimeError("ii and jj must have the same length")
+    for name, t in (("disps_sens", disps_sens), ("targets", targets), ("weights", weights), ("eta", eta)):
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"{name} must be float32")
+    if disps_sens.dim() != 3 or disps_sens.size(0) < num or tuple(disps_sens.shape[1:]) != (ht, wd):
+        raise RuntimeError("disps_sens must have dimensions (num, ht, wd)")
+    if tuple(targets.shape) != (n, 2, ht, wd) or tuple(weights.shape) != (n, 2, ht, wd):
+        raise RuntimeError("targets and weights must have dimensions (n_edges, 2, ht, wd)")
+    if eta.dim() != 3 or tuple(eta.shape[1:]) != (ht, wd):
+        raise RuntimeError("eta must have dimensions (K, ht, wd)")
+    t0, t1, K = int(t0), int(t1), eta.size(0)
+    L = _lib.load()
+    nbytes = L.wgsr_droid_ba_workspace_bytes(num, ht, wd, n, t0, t1, K)
+    if nbytes < 0:
+        _lib.check(1)
+    workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    return dev, num, ht, wd, n, K, t0, t1, workspace, status
+
+
+def _ba_raise(status):
+    word = int(status.item())
+    if word:
+        what = "; ".join(msg for bit, msg in BA_STATUS.items() if word & bit)
+        raise RuntimeError(f"droid_backends.ba: {what} (status {word}); poses and disps are unchanged")
+
+
+def _ba(poses, disps, intrinsics, disps_sens, targets, weights, eta, ii, jj, t0, t1, iterations, lm, ep,
+        motion_only, depth_only, check=True):
+    dev, num, ht, wd, n, K, t0, t1, workspace, status = _ba_prepare(poses, disps, intrinsics, disps_sens, targets,
+                                                                     weights, eta, ii, jj, t0, t1)
+    motion_only = bool(motion_only)
+    dx = torch.zeros(t1 - t0, 6, dtype=torch.float32, device=dev)
+    dz = torch.zeros((0,) if motion_only else (K, ht * wd), dtype=torch.float32, device=dev)
+    L = _lib.load()
+    with torch.cuda.device(dev):
+        _lib.check(L.wgsr_droid_ba(poses.data_ptr(), disps.data_ptr(), intrinsics.data_ptr(), disps_sens.data_ptr(),
+                                   targets.data_ptr(), weights.data_ptr(), eta.data_ptr(), ii.data_ptr(),
+                                   jj.data_ptr(), num, ht, wd, n, K, t0, t1, int(iterations), float(lm), float(ep),
+                                   int(motion_only), int(bool(depth_only)), workspace.data_ptr(), workspace.numel(),
+                                   dx.data_ptr(), None if motion_only else dz.data_ptr(), status.data_ptr(),
+                                   _lib.stream_handle(dev)))
+    if check:
+        _ba_raise(status)
+    return [dx, dz]
+
+
+def ba(*args, **kwargs):
+    """[dx [P, 6], dz [K, ht * wd]]: ``iterations`` Gauss-Newton steps of the
+    dense bundle adjustment; ``poses[t0:t1]`` and the disparities of the
+    frames {t0..t1-1} u set(ii) are updated in place (``motion_only``: poses
+    only, ``dz`` empty; ``depth_only``: disparities only).  The reference's
+    call form: ``ba(poses, disps, intrinsics, disps_sens, targets, weights,
+    eta, ii, jj, t0, t1, iterations, lm, ep, motion_only, depth_only)``.
+
+    The kernels validate the indices on the device; by default the status
+    word is read back after the call and a ``RuntimeError`` names what was
+    wrong (poses and disps are then unchanged).  ``check=False`` skips that
+    read: the call then makes no synchronisation and can be captured in a
+    graph."""
+    if len(args) != 16 or set(kwargs) - {"check"}:
+        raise NotImplementedError("droid_backends.ba: only the reference's call form (poses, disps, ..., depth_only) "
+                                  "is implemented")
+    return _ba(*args, **kwargs)
+
+
+def _ba_system(poses, disps, intrinsics, disps_sens, targets, weights, eta, ii, jj, t0, t1, lm, ep,
+               motion_only=False, check=True):
+    """Diagnostic: one linearisation at the current state, nothing updated.
+    (H [6P, 6P], g [6P]) in float64 = the damped reduced system, C and w
+    [K, ht * wd] (None with ``motion_only``), and the solve's dx [P, 6]."""
+    dev, num, ht, wd, n, K, t0, t1, workspace, status = _ba_prepare(poses, disps, intrinsics, disps_sens, targets,
+                                                                     weights, eta, ii, jj, t0, t1)
+    motion_only = bool(motion_only)
+    P = t1 - t0
+    H = torch.zeros(6 * P, 6 * P, dtype=torch.float64, device=dev)
+    g = torch.zeros(6 * P, dtype=torch.float64, device=dev)
+    dx = torch.zeros(P, 6, dtype=torch.float32, device=dev)
+    C = w = None
+    if not motion_only:
+        C = torch.zeros(K, ht * wd, dtype=torch.float32, device=dev)
+        w = torch.zeros(K, ht * wd, dtype=torch.float32, device=dev)
+    L = _lib.load()
+    with torch.cuda.device(dev):
+        _lib.check(L.wgsr_droid_ba_system(poses.data_ptr(), disps.data_ptr(), intrinsics.data_ptr(),
+                                          disps_sens.data_ptr(), targets.data_ptr(), weights.data_ptr(),
+                                          eta.data_ptr(), ii.data_ptr(), jj.data_ptr(), num, ht, wd, n, K, t0, t1,
+                                          float(lm), float(ep), int(motion_only), workspace.data_ptr(),
+                                          workspace.numel(), H.data_ptr(), g.data_ptr(),
+                                          None if motion_only else C.data_ptr(),
+                                          None if motion_only else w.data_ptr(), dx.data_ptr(), status.data_ptr(),
+                                          _lib.stream_handle(dev)))
+    if check:
+        _ba_raise(status)
+    return H, g, C, w, dx
+
+
 def _not_built(name):
     def op(*args, **kwargs):
         raise NotImplementedError(f"droid_backends.{name} is not built for MI355X yet (csrc/droid.hip has "
-                                  f"frame_distance, depth_filter, iproj and corr_index_*)")
+                                  f"frame_distance, depth_filter, iproj and corr_index_*; csrc/droid_ba.hip has ba)")
     op.__name__ = name
     return op
 
 
-ba = _not_built("ba")
 projmap = _not_built("projmap")
 altcorr_forward = _not_built("altcorr_forward")
 altcorr_backward = _not_built("altcorr_backward")

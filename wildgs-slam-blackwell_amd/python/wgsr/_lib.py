@@ -309,6 +309,17 @@ def load():
         L.wgsr_droid_corr_index_forward.argtypes = [_fp, _fp] + [c_int] * 7 + [_fp, _fp]
         L.wgsr_droid_corr_index_backward.restype = c_int
         L.wgsr_droid_corr_index_backward.argtypes = [_fp, _fp] + [c_int] * 7 + [_fp, _fp]
+        # droid_backends.ba (csrc/droid_ba.hip)
+        L.wgsr_droid_ba_workspace_bytes.restype = ctypes.c_int64
+        L.wgsr_droid_ba_workspace_bytes.argtypes = [c_int] * 7
+        L.wgsr_droid_ba.restype = c_int
+        L.wgsr_droid_ba.argtypes = ([_fp] * 9 + [c_int] * 8 + [ctypes.c_float] * 2 + [c_int] * 2
+                                    + [_fp, ctypes.c_int64] + [_fp] * 4)
+        L.wgsr_droid_ba_stage_events.restype = None
+        L.wgsr_droid_ba_stage_events.argtypes = [ctypes.c_void_p]
+        L.wgsr_droid_ba_system.restype = c_int
+        L.wgsr_droid_ba_system.argtypes = ([_fp] * 9 + [c_int] * 7 + [ctypes.c_float] * 2 + [c_int]
+                                           + [_fp, ctypes.c_int64] + [_fp] * 7)
         L.wgsr_last_error.restype = ctypes.c_char_p
         L.wgsr_last_error.argtypes = []
         L.wgsr_version.restype = ctypes.c_char_p
@@ -351,6 +362,7 @@ EXPORTED_SYMBOLS = (
     "wgsr_sparse_fill_radius", "wgsr_sparse_pack_grads", "wgsr_sparse_unpack_grads",
     "wgsr_droid_frame_distance", "wgsr_droid_depth_filter", "wgsr_droid_iproj",
     "wgsr_droid_corr_index_forward", "wgsr_droid_corr_index_backward",
+    "wgsr_droid_ba_workspace_bytes", "wgsr_droid_ba", "wgsr_droid_ba_system", "wgsr_droid_ba_stage_events",
 )
 
 VIEW_RECORD_FLOATS = 12   # WGSR_VIEW_RECORD_FLOATS

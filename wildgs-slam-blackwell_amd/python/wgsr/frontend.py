@@ -5,6 +5,8 @@
 * ``valid_depth_mask``  DepthVideo.update_valid_depth_mask (depth_video.py:407-442)
 * ``depth_and_pose``    the non-metric branch of DepthVideo.get_depth_and_pose
                         with get_w2c_and_depth's validity flag (mapper.py:574-599)
+* ``ba``                DepthVideo.ba (depth_video.py:351-373): the dense bundle
+                        adjustment (csrc/droid_ba.hip)
 
 poses [num, 7] = (tx, ty, tz, qx, qy, qz, qw), world to camera; disps
 [num, ht, wd]; intrinsics [4] = (fx, fy, cx, cy); device fp32 tensors.
@@ -75,3 +77,30 @@ def depth_and_pose(pose7, disp, mask):
     mask = mask.clone()
     invalid = bool(mask.sum() < MIN_VALID_DEPTHS)
     return depth, mask, pose_to_c2w(pose7), invalid
+
+
+@torch.no_grad()
+def ba(poses, disps, intrinsics, target, weight, eta, ii, jj, t0=1, t1=None, iters=2, lm=1e-4, ep=0.1,
+       motion_only=False, uncertainties_inv=None, mono_disps=None, mono_valid_mask=None):
+    """DepthVideo.ba on the buffers themselves: ``poses`` and ``disps`` are
+    updated in place and the disparities clamped to >= 1e-5.  ``target`` and
+    ``weight`` are the update operator's [1, N, ht, wd, 2]; with
+    ``uncertainties_inv`` [num, ht, wd] the weight of edge e is multiplied by
+    that of its source frame; ``mono_disps`` masked by ``mono_valid_mask``
+    (both [num, ht, wd]) are the sensor disparities, else there are none.
+    ``t1`` None: max(ii, jj) + 1, the one host read."""
+    ht, wd = disps.shape[1], disps.shape[2]
+    if uncertainties_inv is not None:
+        weight = weight * uncertainties_inv[ii][None, :, :, :, None]
+    target = target.view(-1, ht, wd, 2).permute(0, 3, 1, 2).contiguous()
+    weight = weight.view(-1, ht, wd, 2).permute(0, 3, 1, 2).contiguous()
+    if mono_disps is not None and mono_valid_mask is not None:
+        disps_sens = (mono_disps * mono_valid_mask).contiguous()
+    else:
+        disps_sens = torch.zeros_like(disps)
+    if t1 is None:
+        t1 = int(max(ii.max().item(), jj.max().item())) + 1
+    out = droid_backends.ba(poses, disps, intrinsics, disps_sens, target, weight, eta, ii, jj, t0, t1, iters, lm, ep,
+                            motion_only, False)
+    disps.clamp_(min=1e-5)
+    return out

@@ -773,10 +773,10 @@ const char* wgsr_version(void);
 int64_t wgsr_depth_order_offset(void);
 
 /* ---- droid_backends (src/lib/droid.cpp:254-266): the tracker-side ops that
- * feed the mapper, and the correlation lookup (csrc/droid.hip).  poses
- * [num, 7] = (tx, ty, tz, qx, qy, qz, qw), world to camera; disps
- * [num, ht, wd] fp32; intrinsics [4] = (fx, fy, cx, cy); all device memory.
- * projmap and altcorr_* have no entry point yet. */
+ * feed the mapper, and the correlation lookups (csrc/droid.hip,
+ * csrc/droid_altcorr.hip).  poses [num, 7] = (tx, ty, tz, qx, qy, qz, qw),
+ * world to camera; disps [num, ht, wd] fp32; intrinsics [4] = (fx, fy, cx,
+ * cy); all device memory.  projmap has no entry point yet. */
 
 /* Replaces droid_backends.frame_distance (DepthVideo.distance,
  * depth_video.py:205-235): dist[k] = mean induced flow of frame ii[k]'s
@@ -819,6 +819,50 @@ int wgsr_droid_corr_index_forward(const void* volume, const float* coords, int d
  * written, zeros included: the caller needs no memset. */
 int wgsr_droid_corr_index_backward(const float* coords, const void* corr_grad, int dtype, int n, int h1, int w1,
                                    int h2, int w2, int radius, void* volume_grad, void* stream);
+
+/* Replaces droid_backends.altcorr_forward (CorrLayer.forward / AltCorrBlock,
+ * corr.py:93-159; csrc/droid_altcorr.hip): the lookup above on the all-pairs
+ * volume <fmap1[.., y, x, :], fmap2[.., y2, x2, :]>, without the volume.
+ * fmap1 [f1, h1, w1, c] and fmap2 [f2, h2, w2, c], channels last, both of
+ * type `dtype`; coords [b, n, h1, w1, 2] fp32 (x, y), multiplied by
+ * coord_scale (a power of two, so the product is exact: a pyramid level's
+ * 2^-i needs no scaled copy).  Entry e reads maps fmap1[ii[e]] and
+ * fmap2[jj[e]] (device int64 [b]; a null array: map e, and then b <= f1 / f2);
+ * an index outside [0, f) reads nothing and gives that entry NaN.
+ * corr[e, m, iy + (2r+1) ix, y, x] (type corr_dtype: fp32, or fp16 with fp16
+ * maps) = the bilinear blend, around (x0 + ix - r, y0 + iy - r) with (x0, y0)
+ * = coord_scale coords[e, m, y, x], of the taps' dot products; taps outside
+ * the plane are zero.  It is written at corr + e corr_stride_b + m
+ * corr_stride_n + (channel_offset + iy + (2r+1) ix) h1 w1 + y w1 + x
+ * (strides in elements), so one pyramid level lands in its channel slice of
+ * [b, n, levels (2r+1)^2, h1, w1].  Each dot product is accumulated in fp32
+ * (32-channel partial sums, added in order), the blend in fp32, one rounding
+ * to corr_dtype; the weights 1 - dx, 1 - dy are formed as (floor + 1) - x, so
+ * each of the four blend weights is accurate relative to itself even for a
+ * small negative coordinate.  A centre that is not finite, or whose floor is 1e8 or more
+ * in magnitude (compared as a float, before it becomes an int), gives an
+ * all-zero window; no coordinate value reads out of bounds.  Every output
+ * element is written (no memset), nothing synchronises with the host (the call
+ * can be captured in a graph), and the result is bit-reproducible.  c a
+ * positive multiple of 32, radius <= 6; 16-byte loads when fmap2 is 16-byte
+ * aligned, element loads otherwise.  Anything else: WGSR_EINVAL before a
+ * launch. */
+int wgsr_droid_altcorr_forward(const void* fmap1, const void* fmap2, const float* coords, const int64_t* ii,
+                               const int64_t* jj, int dtype, int corr_dtype, int f1, int f2, int b, int n, int h1,
+                               int w1, int h2, int w2, int c, int radius, float coord_scale, void* corr,
+                               int64_t corr_stride_b, int64_t corr_stride_n, int channel_offset, void* stream);
+/* Replaces droid_backends.altcorr_backward (CorrLayer.backward, corr.py:101-
+ * 108): fp32, the plain form (entry e reads maps e, coord_scale 1).  corr_grad
+ * [b, n, (2r+1)^2, h1, w1] contiguous.  fmap1_grad [b, h1, w1, c] and
+ * fmap2_grad [b, h2, w2, c] = the exact adjoint of the forward's definition;
+ * coords_grad [b, n, h1, w1, 2] (may be null) = 0, the reference's contract.
+ * Every element of fmap1_grad is written once.  fmap2_grad is zero-filled on
+ * the stream by this call and then accumulated with the hardware fp32 atomic
+ * add, whose order of arrival varies: fmap2_grad is NOT bit-reproducible from
+ * run to run (fmap1_grad is).  No host synchronisation. */
+int wgsr_droid_altcorr_backward(const float* fmap1, const float* fmap2, const float* coords, const float* corr_grad,
+                                int b, int n, int h1, int w1, int h2, int w2, int c, int radius, float* fmap1_grad,
+                                float* fmap2_grad, float* coords_grad, void* stream);
 
 /* ---- droid_backends.ba (csrc/droid_ba.hip): DROID-SLAM's dense bundle
  * adjustment over n_edges edges (ii[e], jj[e]) with targets / weights

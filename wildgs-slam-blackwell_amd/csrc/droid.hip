@@ -1,7 +1,8 @@
 // droid_backends for gfx950: the tracker-side ops that feed the mapper
 // (frame_distance, depth_filter, iproj) and the per-iteration correlation
-// lookup (corr_index_forward / corr_index_backward).  ba is droid_ba.hip;
-// projmap and altcorr are not built (python/droid_backends raises for them).
+// lookup (corr_index_forward / corr_index_backward).  ba is droid_ba.hip,
+// altcorr droid_altcorr.hip; projmap is not built (python/droid_backends
+// raises for it).
 //
 // Conventions (DROID-SLAM's): poses [num, 7] = (tx, ty, tz, qx, qy, qz, qw),
 // world to camera; disps [num, ht, wd]; intrinsics (fx, fy, cx, cy).  Pixel
@@ -34,6 +35,7 @@
 
 #include "wgsr_common.h"
 #include "wgsr_internal.h"
+#include "droid_corr.h"
 #include "droid_pose.h"
 
 namespace wgsr {
@@ -208,22 +210,15 @@ __global__ __launch_bounds__(256) void k_iproj(const float* __restrict__ poses, 
 // corr_index
 // ---------------------------------------------------------------------------
 constexpr int kCorrPos = 64;  // positions per workgroup (lane <-> position)
-constexpr int kCorrMaxRadius = 6;
-
-__device__ __forceinline__ float to_f32(float v) { return v; }
-__device__ __forceinline__ float to_f32(__half v) { return __half2float(v); }
-template <class T> __device__ __forceinline__ T from_f32(float v);
-template <> __device__ __forceinline__ float from_f32<float>(float v) { return v; }
-template <> __device__ __forceinline__ __half from_f32<__half>(float v) { return __float2half_rn(v); }
 
 struct CorrPosLds {
   int fx[kCorrPos], fy[kCorrPos];    // floor of the lookup centre
   float dx[kCorrPos], dy[kCorrPos];  // its fractional part
 };
 
-// the lookup centre of the workgroup's position `pos` (thread pos < 64).  A
-// centre that is not finite, or too far away for int arithmetic, is moved to
-// where no tap can land: the whole window is zero.
+// the lookup centre of the workgroup's position `pos` (thread pos < 64), by
+// corr_centre's rule (droid_corr.h): a centre that is not finite, or too far
+// away for int arithmetic, gives an all-zero window.
 __device__ __forceinline__ void corr_load_centre(CorrPosLds& L, const float* __restrict__ coords, size_t n, int HW,
                                                  int p, int pos) {
   float x0 = 0.f, y0 = 0.f;
@@ -231,12 +226,11 @@ __device__ __forceinline__ void corr_load_centre(CorrPosLds& L, const float* __r
     x0 = coords[(2 * n) * HW + p];
     y0 = coords[(2 * n + 1) * HW + p];
   }
-  const float flx = floorf(x0), fly = floorf(y0);
-  const bool ok = fabsf(flx) < 1e8f && fabsf(fly) < 1e8f;  // (false for NaN)
-  L.fx[pos] = ok ? (int)flx : -(1 << 29);
-  L.fy[pos] = ok ? (int)fly : -(1 << 29);
-  L.dx[pos] = ok ? x0 - flx : 0.f;
-  L.dy[pos] = ok ? y0 - fly : 0.f;
+  const CorrCentre c = corr_centre(x0, y0);
+  L.fx[pos] = c.fx;
+  L.fy[pos] = c.fy;
+  L.dx[pos] = c.dx;
+  L.dy[pos] = c.dy;
 }
 
 // dynamic LDS: kCorrPos rows of `stride` floats

@@ -1,14 +1,15 @@
 """``droid_backends`` on MI355X: the native module the reference imports in
 ``src/depth_video.py`` and ``src/modules/droid_net/corr.py``
 (bindings: src/lib/droid.cpp:254-266), computed by libwgsr.so's gfx950
-kernels (csrc/droid.hip, include/wgsr.h ``wgsr_droid_*``).
+kernels (csrc/droid*.hip, include/wgsr.h ``wgsr_droid_*``).
 
 Built: ``ba`` (csrc/droid_ba.hip), ``frame_distance``, ``depth_filter``,
-``iproj``, ``corr_index_forward``, ``corr_index_backward`` -- the reference's
-argument order and return shapes (the two lookups return one-element lists).
-Not built yet: ``projmap``, ``altcorr_forward``, ``altcorr_backward``; they
-raise ``NotImplementedError`` naming the op, so a caller sees at once what is
-missing.  Launches go on torch's current stream.
+``iproj``, ``corr_index_forward``, ``corr_index_backward``, and
+``altcorr_forward`` / ``altcorr_backward`` (csrc/droid_altcorr.hip: the
+lookups of the backend's ``FactorGraph.update_lowmem``) -- the reference's
+argument order and return shapes (the lookups return lists).
+Not built: ``projmap``, which the reference's Python never calls; it raises
+``NotImplementedError`` naming the op.  Launches go on torch's current stream.
 """
 from __future__ import annotations
 
@@ -288,14 +289,100 @@ def _ba_system(poses, disps, intrinsics, disps_sens, targets, weights, eta, ii, 
     return H, g, C, w, dx
 
 
-def _not_built(name):
-    def op(*args, **kwargs):
-        raise NotImplementedError(f"droid_backends.{name} is not built for MI355X yet (csrc/droid.hip has "
-                                  f"frame_distance, depth_filter, iproj and corr_index_*; csrc/droid_ba.hip has ba)")
-    op.__name__ = name
-    return op
+# ---------------------------------------------------------------------------
+# on-the-fly correlation
+# ---------------------------------------------------------------------------
+def _altcorr_shapes(fmap1, fmap2, coords, dtypes):
+    if fmap1.dim() != 4 or fmap2.dim() != 4:
+        raise RuntimeError("fmap1 and fmap2 must have dimensions (b, h, w, c), channels last")
+    if fmap1.dtype not in dtypes or fmap2.dtype != fmap1.dtype:
+        names = " or ".join(str(d).replace("torch.", "") for d in dtypes)
+        raise RuntimeError(f"fmap1 and fmap2 must both be {names}, got {fmap1.dtype} and {fmap2.dtype}")
+    if fmap2.size(3) != fmap1.size(3) or fmap1.size(3) <= 0 or fmap1.size(3) % 32 != 0:
+        raise RuntimeError("fmap1 and fmap2 must have the same channel count, a positive multiple of 32")
+    if coords.dim() != 5 or coords.dtype != torch.float32 or coords.size(4) != 2:
+        raise RuntimeError("coords must be a float32 tensor of dimensions (b, n, h1, w1, 2)")
+    return coords.size(0), coords.size(1), fmap1.size(1), fmap1.size(2), fmap2.size(1), fmap2.size(2), fmap1.size(3)
 
 
-projmap = _not_built("projmap")
-altcorr_forward = _not_built("altcorr_forward")
-altcorr_backward = _not_built("altcorr_backward")
+def _altcorr_launch(fmap1, fmap2, coords, ii, jj, radius, coord_scale, out, channel_offset, dev):
+    """One forward launch into ``out`` [b, n, channels, h1, w1] (contiguous) at
+    ``channel_offset``; entry e reads fmap1[ii[e]] and fmap2[jj[e]] (``None``:
+    map e).  Shared by ``altcorr_forward`` and ``wgsr.frontend.AltCorrBlock``."""
+    b, n, h1, w1 = coords.shape[:4]
+    L = _lib.load()
+    with torch.cuda.device(dev):
+        _lib.check(L.wgsr_droid_altcorr_forward(
+            fmap1.data_ptr(), fmap2.data_ptr(), coords.data_ptr(), None if ii is None else ii.data_ptr(),
+            None if jj is None else jj.data_ptr(), _DTYPE_TAG[fmap1.dtype], _DTYPE_TAG[out.dtype], fmap1.size(0),
+            fmap2.size(0), b, n, h1, w1, fmap2.size(1), fmap2.size(2), fmap1.size(3), int(radius),
+            float(coord_scale), out.data_ptr(), out.stride(0), out.stride(1), int(channel_offset),
+            _lib.stream_handle(dev)))
+
+
+def _altcorr_forward(fmap1, fmap2, coords, radius):
+    _contiguous(fmap1=fmap1, fmap2=fmap2, coords=coords)
+    b, n, h1, w1, h2, w2, c = _altcorr_shapes(fmap1, fmap2, coords, (torch.float32, torch.float16))
+    dev = _device_of(fmap1=fmap1, fmap2=fmap2, coords=coords)
+    if fmap1.size(0) != b or fmap2.size(0) != b or tuple(coords.shape[2:4]) != (h1, w1):
+        raise RuntimeError("fmap1 (b, h1, w1, c), fmap2 (b, h2, w2, c) and coords (b, n, h1, w1, 2) do not match")
+    r = int(radius)
+    corr = torch.empty(b, n, (2 * r + 1) ** 2, h1, w1, dtype=fmap1.dtype, device=dev)
+    if corr.numel() == 0:
+        return [corr]
+    _altcorr_launch(fmap1, fmap2, coords, None, None, r, 1.0, corr, 0, dev)
+    return [corr]
+
+
+def _altcorr_backward(fmap1, fmap2, coords, corr_grad, radius):
+    _contiguous(fmap1=fmap1, fmap2=fmap2, coords=coords, corr_grad=corr_grad)
+    b, n, h1, w1, h2, w2, c = _altcorr_shapes(fmap1, fmap2, coords, (torch.float32,))
+    dev = _device_of(fmap1=fmap1, fmap2=fmap2, coords=coords, corr_grad=corr_grad)
+    if fmap1.size(0) != b or fmap2.size(0) != b or tuple(coords.shape[2:4]) != (h1, w1):
+        raise RuntimeError("fmap1 (b, h1, w1, c), fmap2 (b, h2, w2, c) and coords (b, n, h1, w1, 2) do not match")
+    r = int(radius)
+    if corr_grad.dtype != torch.float32 or tuple(corr_grad.shape) != (b, n, (2 * r + 1) ** 2, h1, w1):
+        raise RuntimeError("corr_grad must be a float32 tensor of dimensions (b, n, (2r+1)^2, h1, w1)")
+    fmap1_grad = torch.empty_like(fmap1)
+    fmap2_grad = torch.empty_like(fmap2)
+    coords_grad = torch.empty_like(coords)
+    if b == 0:
+        return [fmap1_grad, fmap2_grad, coords_grad]
+    L = _lib.load()
+    with torch.cuda.device(dev):
+        _lib.check(L.wgsr_droid_altcorr_backward(fmap1.data_ptr(), fmap2.data_ptr(), _lib.ptr(coords),
+                                                 _lib.ptr(corr_grad), b, n, h1, w1, h2, w2, c, r,
+                                                 fmap1_grad.data_ptr(), fmap2_grad.data_ptr(), _lib.ptr(coords_grad),
+                                                 _lib.stream_handle(dev)))
+    return [fmap1_grad, fmap2_grad, coords_grad]
+
+
+def altcorr_forward(*args, **kwargs):
+    """[corr [b, n, (2r+1)^2, h1, w1]]: the correlation lookup computed on the
+    fly (CorrLayer.forward).  ``fmap1`` [b, h1, w1, c] and ``fmap2`` [b, h2,
+    w2, c] channels last, float32 or float16 (corr has their type, accumulated
+    in fp32); ``coords`` [b, n, h1, w1, 2] float32 (x, y).  corr[b, n, iy +
+    (2r+1) ix] is the bilinear sample, at (x + ix - r, y + iy - r), of the
+    pixel's dot products with ``fmap2``: ``corr_index_forward`` of the
+    all-pairs volume, which is never stored.  c a positive multiple of 32."""
+    if len(args) != 4 or kwargs:
+        raise NotImplementedError("droid_backends.altcorr_forward: only the reference's call form "
+                                  "(fmap1, fmap2, coords, radius) is implemented")
+    return _altcorr_forward(*args)
+
+
+def altcorr_backward(*args, **kwargs):
+    """[fmap1_grad, fmap2_grad, coords_grad] of ``altcorr_forward`` (float32
+    only): the adjoint of the forward with respect to the two maps;
+    ``coords_grad`` is all zeros, as in the reference.  ``fmap2_grad`` is
+    accumulated with atomic adds and is not bit-reproducible."""
+    if len(args) != 5 or kwargs:
+        raise NotImplementedError("droid_backends.altcorr_backward: only the reference's call form "
+                                  "(fmap1, fmap2, coords, corr_grad, radius) is implemented")
+    return _altcorr_backward(*args)
+
+
+def projmap(*args, **kwargs):
+    raise NotImplementedError("droid_backends.projmap is not built for MI355X (the reference's Python never calls "
+                              "it); every other name of the module is: csrc/droid.hip, csrc/droid_altcorr.hip, "
+                              "csrc/droid_ba.hip")

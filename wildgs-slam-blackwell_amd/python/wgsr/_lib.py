@@ -309,6 +309,12 @@ def load():
         L.wgsr_droid_corr_index_forward.argtypes = [_fp, _fp] + [c_int] * 7 + [_fp, _fp]
         L.wgsr_droid_corr_index_backward.restype = c_int
         L.wgsr_droid_corr_index_backward.argtypes = [_fp, _fp] + [c_int] * 7 + [_fp, _fp]
+        # droid_backends.altcorr_* (csrc/droid_altcorr.hip)
+        L.wgsr_droid_altcorr_forward.restype = c_int
+        L.wgsr_droid_altcorr_forward.argtypes = ([_fp] * 5 + [c_int] * 12 + [ctypes.c_float, _fp, c_i64, c_i64, c_int]
+                                                 + [_fp])
+        L.wgsr_droid_altcorr_backward.restype = c_int
+        L.wgsr_droid_altcorr_backward.argtypes = [_fp] * 4 + [c_int] * 8 + [_fp] * 4
         # droid_backends.ba (csrc/droid_ba.hip)
         L.wgsr_droid_ba_workspace_bytes.restype = ctypes.c_int64
         L.wgsr_droid_ba_workspace_bytes.argtypes = [c_int] * 7
@@ -362,6 +368,7 @@ EXPORTED_SYMBOLS = (
     "wgsr_sparse_fill_radius", "wgsr_sparse_pack_grads", "wgsr_sparse_unpack_grads",
     "wgsr_droid_frame_distance", "wgsr_droid_depth_filter", "wgsr_droid_iproj",
     "wgsr_droid_corr_index_forward", "wgsr_droid_corr_index_backward",
+    "wgsr_droid_altcorr_forward", "wgsr_droid_altcorr_backward",
     "wgsr_droid_ba_workspace_bytes", "wgsr_droid_ba", "wgsr_droid_ba_system", "wgsr_droid_ba_stage_events",
 )
 

@@ -7,6 +7,9 @@
                         with get_w2c_and_depth's validity flag (mapper.py:574-599)
 * ``ba``                DepthVideo.ba (depth_video.py:351-373): the dense bundle
                         adjustment (csrc/droid_ba.hip)
+* ``AltCorrBlock``      the correlation lookups of FactorGraph.update_lowmem
+                        (corr.py AltCorrBlock), one fused launch per pyramid
+                        level (csrc/droid_altcorr.hip)
 
 poses [num, 7] = (tx, ty, tz, qx, qy, qz, qw), world to camera; disps
 [num, ht, wd]; intrinsics [4] = (fx, fy, cx, cy); device fp32 tensors.
@@ -14,6 +17,7 @@ poses [num, 7] = (tx, ty, tz, qx, qy, qz, qw), world to camera; disps
 from __future__ import annotations
 
 import torch
+import torch.nn.functional as F
 
 import droid_backends
 
@@ -104,3 +108,71 @@ def ba(poses, disps, intrinsics, target, weight, eta, ii, jj, t0=1, t1=None, ite
                             motion_only, False)
     disps.clamp_(min=1e-5)
     return out
+
+
+class AltCorrBlock:
+    """The on-the-fly correlation pyramid of the global bundle adjustment's
+    update loop.  ``fmaps`` [B, N, C, H, W] (any float type; the video buffer's
+    is float16) become ``pyramid``: ``num_levels`` channels-last maps [B, N,
+    H // 2^i, W // 2^i, C] of ``fmaps`` / 4, each level the 2 x 2 average of
+    the one before, in ``fmaps``' own type.
+
+    ``block(coords, ii, jj)`` with ``coords`` [B, E, H, W, 2] (x, y) and frame
+    indices ``ii``, ``jj`` [E] returns float32 [B, E, num_levels (2r+1)^2, H,
+    W]: for level i the lookup of frame ii's level-0 features in frame jj's
+    level-i map around ``coords`` / 2^i.  Each level is one launch that reads
+    the pyramid in place through the index arrays (batch b reads map b N +
+    ii), converts on load, scales the coordinates itself and writes its
+    channel slice of the result: no per-edge copies of the maps, no
+    concatenation.  ``coords`` [B, E, H, W, S, 2] gives [B, E, num_levels
+    (2r+1)^2, H, W, S].
+
+    Inference only: the result carries no autograd graph.  Training goes
+    through ``droid_backends.altcorr_forward`` / ``altcorr_backward``."""
+
+    def __init__(self, fmaps, num_levels=4, radius=3):
+        self.num_levels = num_levels
+        self.radius = radius
+        B, N, C, H, W = fmaps.shape
+        level = fmaps.reshape(B * N, C, H, W) / 4.0
+        self.pyramid = []
+        for i in range(num_levels):
+            self.pyramid.append(level.permute(0, 2, 3, 1).contiguous().view(B, N, H // 2 ** i, W // 2 ** i, C))
+            if i + 1 < num_levels:
+                level = F.avg_pool2d(level, kernel_size=2, stride=2)
+
+    @torch.no_grad()
+    def __call__(self, coords, ii, jj):
+        samples = coords.dim() == 6
+        if coords.dim() not in (5, 6) or coords.size(-1) != 2 or coords.dtype != torch.float32:
+            raise RuntimeError("coords must be a float32 tensor of dimensions (B, E, H, W, 2) or (B, E, H, W, S, 2)")
+        B, N, H, W, C = self.pyramid[0].shape
+        if self.pyramid[0].dtype not in (torch.float32, torch.float16) or C % 32 != 0:
+            raise RuntimeError("the feature maps must be float32 or float16 with a multiple of 32 channels")
+        dev =droid_backends._device_of(coords=coords, fmaps=self.pyramid[0])
+        E = coords.size(1)
+        if coords.size(0) != B or tuple(coords.shape[2:4]) != (H, W):
+            raise RuntimeError("coords must have the feature maps' batch size, height and width")
+        S = coords.size(4) if samples else 1
+        # the kernel's coords are [entries, samples, H, W, 2]
+        if samples:
+            coords = coords.permute(0, 1, 4, 2, 3, 5)
+        coords = coords.reshape(B * E, S, H, W, 2).contiguous()
+        index = []
+        for name, t in (("ii", ii), ("jj", jj)):
+            t = torch.as_tensor(t).to(dev, torch.int64).reshape(-1)
+            if t.numel() != E:
+                raise RuntimeError(f"{name} must have one frame index per edge")
+            if B > 1:
+                t = (torch.arange(B, device=dev)[:, None] * N + t[None]).reshape(-1)
+            index.append(t.contiguous())
+        rd2 = (2 * self.radius + 1) ** 2
+        out = torch.empty(B * E, S, self.num_levels * rd2, H, W, dtype=torch.float32, device=dev)
+        if out.numel():
+            fmap1 = self.pyramid[0].view(B * N, H, W, C)
+            for i, level in enumerate(self.pyramid):
+                droid_backends._altcorr_launch(fmap1, level.view((B * N,) + level.shape[2:]), coords, index[0],
+                                               index[1], self.radius, 2.0 ** -i, out, i * rd2, dev)
+        if samples:
+            return out.view(B, E, S, -1, H, W).permute(0, 1, 3, 4, 5, 2).contiguous()
+        return out.view(B, E, -1, H, W)

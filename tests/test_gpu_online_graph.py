@@ -46,41 +46,59 @@ def _backward(args, cam, fwd, W, H, dcol, ddep):
                                            fwd[3], fwd[0], fwd[4], fwd[5], False)
 
 
-def test_capacity_forward_matches_and_overflow_zeroes_gradients():
+def test_capacity_forward_matches_and_overflow_zeroes_gradients(monkeypatch):
     from diff_gaussian_rasterization import _C
-    from wgsr.mapping import rasterize_forward_cap
+    from wgsr.mapping import check_tile_lists, rasterize_forward_cap
     args, cam, W, H = _scene()
     xyz, opac, scales, rots, shs = args
     bg = torch.zeros(3, device=DEV)
     e = torch.empty(0, device=DEV)
-    ref = _C.rasterize_gaussians(bg, xyz, e, opac, scales, rots, 1.0, e, cam["viewmatrix"], cam["projmatrix"],
-                                 cam["projmatrix_raw"], cam["tanfovx"], cam["tanfovy"], H, W, shs, 0, cam["campos"],
-                                 False, False)
-    N = ref[0]
-    assert N > 1000
-    counts = torch.zeros(5, dtype=torch.int32, device=DEV)
-    out = rasterize_forward_cap(bg, xyz, opac, scales, rots, shs, 0, cam, H, W, N + 12345, counts)
-    c = counts.cpu().tolist()
-    assert c[0] == N and c[3] == 0 and 0 < c[2] <= c[1] <= N and c[4] == c[2]
-    for i in (1, 2, 6, 7, 8):
-        assert torch.equal(out[i], ref[i]), i
     g = torch.Generator(device=DEV).manual_seed(1)
     dcol = torch.randn(3, H, W, device=DEV, generator=g)
     ddep = torch.randn(1, H, W, device=DEV, generator=g)
-    gr = _backward(args, cam, ref, W, H, dcol, ddep)
-    gc = _backward(args, cam, out, W, H, dcol, ddep)
-    for a, b in zip(gr, gc):
-        assert torch.equal(a, b)
+    counts = torch.zeros(5, dtype=torch.int32, device=DEV)
+    bad = torch.zeros(3, dtype=torch.int32, device=DEV)
+
+    def equal_to_host_forward():
+        ref = _C.rasterize_gaussians(bg, xyz, e, opac, scales, rots, 1.0, e, cam["viewmatrix"], cam["projmatrix"],
+                                     cam["projmatrix_raw"], cam["tanfovx"], cam["tanfovy"], H, W, shs, 0,
+                                     cam["campos"], False, False)
+        N = ref[0]
+        assert N > 1000
+        counts.zero_()
+        out = rasterize_forward_cap(bg, xyz, opac, scales, rots, shs, 0, cam, H, W, N + 12345, counts)
+        c = counts.cpu().tolist()
+        assert c[0] == N and c[3] == 0 and 0 < c[2] <= c[1] <= N and c[4] == c[2]
+        for i in (1, 2, 6, 7, 8):
+            assert torch.equal(out[i], ref[i]), i
+        bad.zero_()
+        for f in (ref, out):
+            check_tile_lists(f, xyz, cam, H, W, 0, shs, bad)
+        assert bad.tolist() == [0, 0, 0]
+        gr = _backward(args, cam, ref, W, H, dcol, ddep)
+        gc = _backward(args, cam, out, W, H, dcol, ddep)
+        for a, b in zip(gr, gc):
+            assert torch.equal(a, b)
+        return ref, out, gr
+
+    # 4 x 4-tile bins (10 x 8 tiles -> 3 x 2 bins): the per-bin depth sort hands
+    # its sorted bins to k_expand_bins instead of emitting the lists itself
+    monkeypatch.setenv("WGSR_BIN_SHIFT", "2")
+    equal_to_host_forward()
+    monkeypatch.setenv("WGSR_BIN_SHIFT", "0")
+    with pytest.raises(RuntimeError, match="capacity mode needs sort bins"):
+        rasterize_forward_cap(bg, xyz, opac, scales, rots, shs, 0, cam, H, W, 1 << 20, counts)
+    # the frame's default (2 x 2-tile bins: the sort emits the lists)
+    monkeypatch.delenv("WGSR_BIN_SHIFT")
+    ref, out, gr = equal_to_host_forward()
+    N = ref[0]
     # overflow: flagged, no host error, every gradient zero
     counts.zero_()
     small = rasterize_forward_cap(bg, xyz, opac, scales, rots, shs, 0, cam, H, W, N // 3, counts)
     c = counts.cpu().tolist()
     assert c[0] == N and c[3] == 1 and c[4] == min(c[2], N // 3)
     # the truncated forward's tile lists stay inside the capacity-sized region
-    from wgsr.mapping import check_tile_lists
-    bad = torch.zeros(3, dtype=torch.int32, device=DEV)
-    for f in (ref, out, small):
-        check_tile_lists(f, xyz, cam, H, W, 0, shs, bad)
+    check_tile_lists(small, xyz, cam, H, W, 0, shs, bad)
     assert bad.tolist() == [0, 0, 0]
     # (and it sees a broken one: tile 0's range -- the image buffer's first
     # word pair -- pointed past the region)

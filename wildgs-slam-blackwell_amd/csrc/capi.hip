@@ -44,6 +44,10 @@ struct HostCounters {
 // one pinned block + event per (host thread, device): an event recorded on a
 // stream must belong to that stream's device
 constexpr int kMaxDevices = 64;
+int device_slot() {  // the current device's slot in a thread_local per-device table (-1: none)
+  int dev = 0;
+  return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kMaxDevices ? dev : -1;
+}
 // The binning buffer's size is known only after the forward's one host wait;
 // allocating it there put the allocation (~10 us of the caller's allocator)
 // on the GPU's critical path.  The previous forward of the same shape on this
@@ -57,9 +61,8 @@ struct BinningGuess {
 };
 BinningGuess& binning_guess() {
   thread_local BinningGuess g[kMaxDevices];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) dev = 0;
-  return g[dev];
+  const int dev = device_slot();
+  return g[dev < 0 ? 0 : dev];
 }
 
 // WGSR_PUBLISH_COUNTS=0: the blit-kernel copy + event wait for every forward
@@ -73,9 +76,8 @@ bool publish_counts() {
 
 HostCounters& host_counters() {
   thread_local HostCounters per_dev[kMaxDevices];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) dev = 0;
-  HostCounters& hc = per_dev[dev];
+  const int dev = device_slot();
+  HostCounters& hc = per_dev[dev < 0 ? 0 : dev];
   if (!hc.buf) {
     void* p = nullptr;
     if (hipHostMalloc(&p, kCounterBytes, hipHostMallocDefault) != hipSuccess) p = nullptr;
@@ -112,11 +114,10 @@ struct DevCounters {
 // sort costs more than k_expand_bins' 4x wider grid (140.8 vs 131.3 us).
 bool bds_emit(int bshift) { return bshift <= 1; }
 
-
 DevCounters* dev_counters(hipStream_t s) {
   thread_local DevCounters per_dev[kMaxDevices];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return nullptr;
+  const int dev = device_slot();
+  if (dev < 0) return nullptr;
   DevCounters& dc = per_dev[dev];
   if (!dc.buf && !dc.failed) {
     void* p = nullptr;
@@ -150,9 +151,12 @@ int num_bits(uint32_t n) {
 namespace {
 
 // ---- optional per-stage timing with HIP events on the caller's stream -----
-const char* const kStageNames[WGSR_NUM_STAGES] = {"preprocess", "depth_sort", "offsets_scan", "duplicate",
-                                                  "tile_sort", "ranges", "render_fwd", "render_bwd",
-                                                  "gauss_bwd", "dist_cuda2"};
+enum Stage { kStPreprocess, kStDepthSort, kStOffsetsScan, kStDuplicate, kStTileSort, kStRanges, kStRenderFwd,
+             kStRenderBwd, kStGaussBwd, kStDistCuda2, kNumStages };
+const char* const kStageNames[] = {"preprocess", "depth_sort", "offsets_scan", "duplicate", "tile_sort",
+                                   "ranges",     "render_fwd", "render_bwd",   "gauss_bwd", "dist_cuda2"};
+static_assert(kNumStages == WGSR_NUM_STAGES && sizeof(kStageNames) / sizeof(kStageNames[0]) == kNumStages,
+              "Stage, kStageNames and WGSR_NUM_STAGES list the same stages in the same order");
 struct Prof {
   uint32_t mask = 0;  // stages timed (bit i: stage i)
   struct Rec { int stage; hipEvent_t a, b; };
@@ -182,10 +186,10 @@ struct Prof {
 Prof g_prof;  // process-wide; the bench is single-threaded per rank
 
 struct StageTimer {
-  int stage;
+  Stage stage;
   hipStream_t s;
   hipEvent_t a = nullptr;
-  StageTimer(int st, hipStream_t str) : stage(st), s(str) {
+  StageTimer(Stage st, hipStream_t str) : stage(st), s(str) {
     if (((g_prof.mask >> st) & 1u) && (a = g_prof.get()) && hipEventRecord(a, s) != hipSuccess) a = nullptr;
   }
   ~StageTimer() {
@@ -202,7 +206,8 @@ struct Grid {
       : gx((a.W + kTile - 1) / kTile), gy((a.H + kTile - 1) / kTile), nt(gx * gy) {}
 };
 
-int tile_sort_bits(const Grid& g) { return num_bits((uint32_t)g.nt) > 0 ? num_bits((uint32_t)g.nt) : 1; }
+// key bits of a radix sort over ids in [0, n): at least 1
+int sort_bits(int n) { return num_bits((uint32_t)n) > 0 ? num_bits((uint32_t)n) : 1; }
 
 // Sort-bin shift (Bins, wgsr_common.h): the duplicate + radix sort work on
 // (Gaussian, bin) pairs of 2^s x 2^s tiles, and k_expand_bins cuts the sorted
@@ -224,35 +229,31 @@ int bin_shift(const wgsr_raster_args& a) {
   // bin ids fit the key's low 16 bits, list lengths the packed scan's 16 bits
   return sh > 0 && g.nt > 65535 ? 0 : sh;
 }
-// WGSR_DEPTH_SORT=full: the depth sort as four 8-bit passes over the whole
-// 32-bit keys (the reference schedule for A/B runs and the parity tests);
-// default: three passes over the visible key range (launch_depth_sort)
-bool depth_sort_full() {
+// What gives the tile lists their depth order (WGSR_DEPTH_SORT).
+// kBins, the default whenever sort bins are on: each bin's entries are ordered
+// by depth after the bin sort (k_bin_depth_sort: the pairs are duplicated in
+// index order, no Gaussian depth order exists).  A/B, ms/step: 100k 512x384
+// SH0 0.218 -> 0.190; 200k / 500k / 1M at 1080p SH3 0.720 -> 0.674, 0.712 ->
+// 0.696, 0.807 -> 0.801.
+// kGlobal ("global", and the default without sort bins): the Gaussian-level
+// depth sort ahead of the duplication, three passes over the visible key
+// range (launch_depth_sort) -- the previous schedule, and the one whose depth
+// order wgsr_depth_order_offset exposes.
+// kFull ("full"): that sort as four 8-bit passes over the whole 32-bit keys
+// (the reference schedule for A/B runs and the parity tests).
+enum class DepthSched { kBins, kGlobal, kFull };
+DepthSched depth_schedule(int bshift) {
   const char* e = getenv("WGSR_DEPTH_SORT");  // read per call: tests compare the modes
-  return e && strcmp(e, "full") == 0;
+  if (e && strcmp(e, "full") == 0) return DepthSched::kFull;
+  if (!bshift || (e && strcmp(e, "global") == 0)) return DepthSched::kGlobal;
+  return DepthSched::kBins;
 }
-// With sort bins the default orders each bin's entries by depth after the bin
-// sort (k_bin_depth_sort: the pairs are duplicated in index order, no
-// Gaussian depth order exists); WGSR_DEPTH_SORT=global|full keeps the
-// Gaussian-level depth sort ahead of the duplication (the previous schedule,
-// and the one whose depth order wgsr_depth_order_offset exposes).
-// The default whenever sort bins are on (A/B, ms/step: 100k 512x384 SH0
-// 0.218 -> 0.190; 200k / 500k / 1M at 1080p SH3 0.720 -> 0.674, 0.712 ->
-// 0.696, 0.807 -> 0.801).  WGSR_DEPTH_SORT=global|full keeps the
-// Gaussian-level sort.
-// ... unless the bins average more than this many entries (the host sees the
-// bin-pair count at its one wait and then falls back to the Gaussian-level
+// ... kBins unless the bins average more than this many entries (the host sees
+// the bin-pair count at its one wait and then falls back to the Gaussian-level
 // sort; WGSR_BIN_DEPTH_MAX_AVG overrides)
 size_t bin_depth_max_avg() {
   const char* e = getenv("WGSR_BIN_DEPTH_MAX_AVG");  // (per call: tests force the fallback)
   return e ? (size_t)strtoull(e, nullptr, 10) : (size_t)6144;
-}
-bool depth_sort_bins(const wgsr_raster_args& a, int bshift) {
-  if (!bshift) return false;
-  const char* e = getenv("WGSR_DEPTH_SORT");
-  if (e && (strcmp(e, "full") == 0 || strcmp(e, "global") == 0)) return false;
-  (void)a;
-  return true;
 }
 constexpr int kDepthBits = 32;
 constexpr bool kFullDepthInAlt = ((kDepthBits + 7) / 8) % 2 == 1;
@@ -296,6 +297,330 @@ int validate(const wgsr_raster_args* a) {
   } while (0)
 
 void* call_alloc(wgsr_alloc_fn fn, void* ctx, size_t bytes) { return fn ? fn(ctx, bytes) : nullptr; }
+
+// ---- the steps of a forward (wgsr_rasterize_forward, wgsr_rasterize_forward_cap) ----
+// What the steps share: the caller's arguments, stream and outputs, the geometry and image
+// buffers with their layouts, the sort-bin shift and the counter block the call accumulates into.
+struct Fwd {
+  const wgsr_raster_args& a;
+  hipStream_t s;
+  Grid grid; GeomLayout GL; ImageLayout IL;
+  int bshift;
+  float *out_color, *out_depth, *out_opacity;
+  int32_t* n_touched;
+  void *geom = nullptr, *image = nullptr;  // (alloc)
+  uint32_t* counter = nullptr;             // the counter block in use (kCounterBytes)
+  template <typename T> T* g(size_t off) const { return at<T>(geom, off); }
+  template <typename T> T* im(size_t off) const { return at<T>(image, off); }
+  int alloc(wgsr_alloc_fn geom_alloc, wgsr_alloc_fn image_alloc, void* ctx) {
+    if (!(geom = call_alloc(geom_alloc, ctx, GL.total)))
+      return set_error(WGSR_EALLOC, "geometry buffer allocation failed");
+    if (!(image = call_alloc(image_alloc, ctx, IL.total)))
+      return set_error(WGSR_EALLOC, "image buffer allocation failed");
+    return WGSR_OK;
+  }
+};
+
+// The binning buffer.  Its layout is sized by upstream's num_rendered
+// (returned to the caller and handed back to the backward), so both sides
+// agree on it; with sort bins the per-tile lists follow it (2^2s entries per
+// bin pair); then, for the per-bin depth sort, the scratch of the bins beyond
+// one LDS tile (two uint2 ping-pong arrays; not the list region, which the
+// same kernel now writes).
+struct BinningPlan {
+  BinLayout BL;
+  size_t lists_bytes, bds_bytes, total;
+  BinningPlan(size_t N_rect, size_t N_bin, int bshift, bool bin_depth)
+      : BL(N_rect), lists_bytes(bshift ? align256(4 * (N_bin << (2 * bshift))) : 0),
+        bds_bytes(bin_depth ? align256(16 * N_bin) : 0), total(BL.total + lists_bytes + bds_bytes) {}
+};
+
+// ---- counts readback: the forward's one host wait ----
+// upstream num_rendered, exact (Gaussian, tile) pairs (<= N_rect), (Gaussian,
+// bin) pairs, k_preprocess's error flags; published: they came through the
+// mailbox (which carries no depth key range: read_depth_range)
+struct Counts {
+  size_t N_rect, N, N_bin;
+  uint32_t flags;
+  bool published;
+};
+
+// The pair counts are known once k_preprocess is done: copy them to pinned
+// host memory behind it and let the depth sort + scan run while the host
+// waits for them, allocates the binning buffer and queues the rest.
+// *pub: for the scan that follows; set when that scan publishes the counts.
+int start_counts_readback(const Fwd& f, bool bin_depth, HostCounters& hc, PublishJob* pub) {
+  if (!hc.buf || !hc.ev) return set_error(WGSR_EHIP, "pinned counter buffer / event allocation failed");
+  // (with the per-bin depth sort nothing would overlap the copy on the side
+  // stream, whose start waits out an event round trip: copy in stream order)
+  // per-bin default: the scan's first wave publishes the counts (PublishJob)
+  if (bin_depth && hc.mbox) {
+    // (no event behind it: an event record makes the runtime end the kernel
+    // with a system-scope release, ~6 us before the next kernel starts; the
+    // wait checks the stream itself instead)
+    // (24-bit sequence numbers, never 0: the record's initial value)
+    *pub = PublishJob{f.counter, hc.mbox, hc.seq = (hc.seq % 0xFFFFFFu) + 1u};
+  } else if (hc.side && !bin_depth) {
+    HIPCHK(hipEventRecord(hc.pre, f.s));
+    HIPCHK(hipStreamWaitEvent(hc.side, hc.pre, 0));
+    HIPCHK(hipMemcpyAsync(hc.buf, f.counter, kCounterBytes, hipMemcpyDeviceToHost, hc.side));
+    HIPCHK(hipEventRecord(hc.ev, hc.side));
+  } else {
+    HIPCHK(hipMemcpyAsync(hc.buf, f.counter, kCounterBytes, hipMemcpyDeviceToHost, f.s));
+    HIPCHK(hipEventRecord(hc.ev, f.s));
+  }
+  return WGSR_OK;
+}
+
+int wait_counts(const Fwd& f, HostCounters& hc, const PublishJob& pub, Counts* c) {
+  if (!pub.counter) {  // a copy is on its way
+    HIPCHK(hipEventSynchronize(hc.ev));
+  } else {
+    uint4 rec = make_uint4(0u, 0u, 0u, 0u);
+    // spin on the published word; every 1024 polls the stream is checked,
+    // so a failed stream ends the wait (and a publish that never became
+    // visible falls back to a copy)
+    // (one aligned 16-byte load: the record is written by one 16-byte store)
+    auto poll = [&]() {
+      asm volatile("" ::: "memory");  // (a fresh load every poll: the GPU writes the record)
+      const __m128i v = _mm_load_si128(reinterpret_cast<const __m128i*>(const_cast<const uint4*>(hc.mbox)));
+      _mm_storeu_si128(reinterpret_cast<__m128i*>(&rec), v);
+      return (rec.x >> 8) == pub.seq;
+    };
+    uint32_t polls = 0;
+    while (!poll()) {
+      _mm_pause();
+      if ((++polls & 1023u) == 0) {
+        const hipError_t q = hipStreamQuery(f.s);
+        if (q == hipErrorNotReady) continue;
+        HIPCHK(q);
+        // the stream is done: the record may still be in flight to host
+        // memory (a posted write) -- a few more polls before giving up on it
+        bool seen = false;
+        for (int k = 0; k < (1 << 16) && !(seen = poll()); ++k) _mm_pause();
+        if (seen) break;
+        hc.mbox = nullptr;  // (not visible on this system: copies from now on)
+        break;
+      }
+    }
+    if (hc.mbox && !(rec.x & 0x80u)) {
+      *c = Counts{rec.y, rec.z, rec.w, rec.x & 0x7Fu, true};
+      return WGSR_OK;
+    }
+    // not published, or a count beyond 32 bits: the block itself
+    HIPCHK(hipMemcpyAsync(hc.buf, f.counter, kCounterBytes, hipMemcpyDeviceToHost, f.s));
+    HIPCHK(hipStreamSynchronize(f.s));
+  }
+  *c = Counts{0, 0, 0, hc.buf[1], false};
+  const uint64_t* partial = reinterpret_cast<const uint64_t*>(hc.buf + 4);
+  for (int i = 0; i < kRectPairLanes; ++i) {
+    c->N_rect += partial[i];
+    c->N += partial[kRectPairLanes + i];
+    c->N_bin += partial[2 * kRectPairLanes + i];
+  }
+  return WGSR_OK;
+}
+
+// After wait_counts: the maxima of the visible depth keys and of their complements.  (The
+// published counts carry no key range: the bins-too-full switch reads the block, rarely.)
+int read_depth_range(const Fwd& f, HostCounters& hc, const Counts& c, uint32_t* hi, uint32_t* nlo) {
+  if (c.published) {
+    HIPCHK(hipMemcpyAsync(hc.buf, f.counter, kCounterBytes, hipMemcpyDeviceToHost, f.s));
+    HIPCHK(hipStreamSynchronize(f.s));
+  }
+  const uint32_t* rw = hc.buf + kDepthRangeOffset / 4;
+  *hi = *nlo = 0;
+  for (int i = 0; i < kRectPairLanes; ++i) {
+    *hi = rw[i] > *hi ? rw[i] : *hi;
+    *nlo = rw[kRectPairLanes + i] > *nlo ? rw[kRectPairLanes + i] : *nlo;
+  }
+  return WGSR_OK;
+}
+
+// ---- depth order of the Gaussians (culled ones carry key 0xFFFFFFFF -> last) ----
+// What k_preprocess's workgroups zero (no memset launch): the next forward's counter block,
+// the depth sort's superblock sums and, with sort bins, the dual scan's superblock sums.
+ZeroJob preprocess_zero_job(const Fwd& f, const DevCounters* dc, DepthSched sched) {
+  const size_t P = (size_t)f.a.P;
+  ZeroJob zj{};
+  auto add = [&](void* p, size_t words) {
+    if (words) { zj.p[zj.count] = static_cast<float*>(p); zj.n[zj.count++] = words; }
+  };
+  if (dc) add(dc->buf + (size_t)(dc->parity ^ 1) * (kCounterBytes / 4), kCounterBytes / 4);
+  size_t sup_off = depth_sort_sup_offset_words(P);
+  const size_t sup_words = sched == DepthSched::kFull     ? sort_sup_words(P, 0, kDepthBits, &sup_off)
+                           : sched == DepthSched::kGlobal ? depth_sort_sup_words(P)
+                                                          : 0;
+  add(f.g<uint32_t>(f.GL.hist) + sup_off, sup_words);
+  if (f.bshift) add(f.g<float>(f.GL.bsup), 2 * kScanSupStride * packed_scan_supers(P));
+  return zj;
+}
+
+// The Gaussian-level depth sort: kFull's four passes, else launch_depth_sort
+// (kGlobal, and kBins' fallback when the bins are too full).  zero_sup: the
+// sort's superblock sums were not in k_preprocess's zero job.
+int queue_depth_sort(const Fwd& f, bool full, bool zero_sup, const uint32_t** depth_order) {
+  const GeomLayout& GL = f.GL;
+  const size_t P = (size_t)f.a.P;
+  uint32_t *dkey = f.g<uint32_t>(GL.dkey), *dkey_alt = f.g<uint32_t>(GL.dkey_alt), *dval = f.g<uint32_t>(GL.dval),
+           *dval_alt = f.g<uint32_t>(GL.dval_alt), *hist = f.g<uint32_t>(GL.hist);
+  StageTimer T(kStDepthSort, f.s);
+  if (full) {
+    const bool sup_zeroed = sort_sup_words(P, 0, kDepthBits, nullptr) != 0;  // (preprocess_zero_job)
+    bool in_alt = false;
+    STAGE(f.a, f.s, radix_sort_pairs(dkey, dkey_alt, dval, dval_alt, true, P, 0, kDepthBits, hist,
+                                     f.g<uint32_t>(GL.totals), f.s, &in_alt, nullptr, nullptr, sup_zeroed));
+    if (in_alt != kFullDepthInAlt) return set_error(WGSR_EHIP, "internal: depth sort parity");
+    *depth_order = kFullDepthInAlt ? dval_alt : dval;
+    return WGSR_OK;
+  }
+  if (zero_sup)
+    HIPCHK(hipMemsetAsync(hist + depth_sort_sup_offset_words(P), 0, 4 * depth_sort_sup_words(P), f.s));
+  STAGE(f.a, f.s, launch_depth_sort(dkey, dkey_alt, dval, dval_alt, P, f.counter + kDepthRangeOffset / 4,
+                                    f.counter + 2, hist, f.s));
+  *depth_order = dval_alt;
+  return WGSR_OK;
+}
+
+// in depth order: duplicate-slot offsets of the exact tile lists (the
+// backward's record slots; Gaussian -> first slot), and with sort bins the
+// bin-pair offsets -- their down-sweep writes the pairs, after the binning
+// buffer exists
+int queue_scan(const Fwd& f, const uint32_t* depth_order, const PublishJob& pj) {
+  const GeomLayout& GL = f.GL;
+  StageTimer T(kStOffsetsScan, f.s);
+  if (f.bshift) {  // block sums of (list length, bins) in depth order; k_duplicate_bins finishes the scan
+    STAGE(f.a, f.s, packed_scan_blocks(f.g<uint32_t>(GL.tb), 1, depth_order, (size_t)f.a.P, f.g<uint32_t>(GL.bsum),
+                                       f.s, f.g<uint2>(GL.bsup), pj));
+  } else {
+    STAGE(f.a, f.s, exclusive_scan_gather(&f.g<ListRec>(GL.lrec)->w.w, depth_order, (size_t)f.a.P,
+                                          f.g<uint32_t>(GL.offs), f.g<uint32_t>(GL.slot_start),
+                                          f.g<uint32_t>(GL.bsum), f.g<uint32_t>(GL.counter), f.s,
+                                          sizeof(ListRec) / 4));
+  }
+  return WGSR_OK;
+}
+
+// the scan again, after the host wait changed the depth order: its superblock sums zeroed by
+// a memset (k_preprocess zeroed them for the first scan), and nothing to publish
+int requeue_scan(const Fwd& f, const uint32_t* depth_order) {
+  const size_t sup_bytes = sizeof(uint2) * kScanSupStride * packed_scan_supers((size_t)f.a.P);
+  if (f.bshift) HIPCHK(hipMemsetAsync(f.g<uint2>(f.GL.bsup), 0, sup_bytes, f.s));
+  return queue_scan(f, depth_order, PublishJob{});
+}
+
+// After launch_depth_sort and the host wait: depths spanning more than the three passes' bits get
+// one more stable pass over the bits above them, then the scan again in the final order.
+int queue_depth_fixup(const Fwd& f, HostCounters& hc, const Counts& c, const uint32_t** depth_order) {
+  const GeomLayout& GL = f.GL;
+  uint32_t hi = 0, nlo = 0;
+  if (int e = read_depth_range(f, hc, c, &hi, &nlo)) return e;
+  const DepthKeyPlan pl = depth_key_plan(hi, ~nlo);
+  if (pl.extra_bits <= 0) return WGSR_OK;
+  bool alt = false;
+  { StageTimer T(kStDepthSort, f.s);
+  STAGE(f.a, f.s, radix_sort_pairs(f.g<uint32_t>(GL.dkey_alt), f.g<uint32_t>(GL.dkey), f.g<uint32_t>(GL.dval_alt),
+                                   f.g<uint32_t>(GL.dval), false, (size_t)f.a.P, pl.extra_shift, pl.R,
+                                   f.g<uint32_t>(GL.hist), f.g<uint32_t>(GL.totals), f.s, &alt)); }
+  *depth_order = f.g<uint32_t>(alt ? GL.dval : GL.dval_alt);
+  return requeue_scan(f, *depth_order);
+}
+
+// ---- tile lists + render: the tail of both forwards ----
+// duplicate -> bin / tile sort -> per-bin depth sort -> expand or ranges ->
+// render, over NL sorted pairs: (Gaussian, bin) pairs, or with bin shift 0
+// the exact (Gaussian, tile) pairs themselves.  depth_order: rank -> Gaussian
+// (null: index order); bin_depth: each bin is ordered by depth after the bin
+// sort.  ndev (capacity mode): NL is the capacity the buffers and grids are
+// sized for and *ndev the live pair count, read on the device.
+int queue_lists_and_render(const Fwd& f, void* binning, const BinningPlan& plan, const uint32_t* depth_order,
+                           bool bin_depth, size_t NL, const uint32_t* ndev) {
+  const wgsr_raster_args& a = f.a;
+  hipStream_t s = f.s;
+  const int bshift = f.bshift;
+  const BinLayout& BL = plan.BL;
+  uint32_t* lists = at<uint32_t>(binning, bshift ? BL.total : BL.point_g);
+  uint2 *ranges = f.im<uint2>(f.IL.ranges), *tile_m = f.im<uint2>(f.IL.tile_m);
+  uint32_t *tile_len = f.im<uint32_t>(f.IL.tile_len), *meta = f.im<uint32_t>(f.IL.meta);
+  const uint32_t *sorted_keys = nullptr, *sorted_gid = nullptr;
+  bool emit = false, bounds_done = false;
+  if (NL > 0) {
+    const int bits = sort_bits(bshift ? Bins(f.grid.gx, f.grid.gy, bshift).n : f.grid.nt);
+    // the LSD sort alternates buffers every pass: start the payload in the
+    // buffer that makes it end in point_g
+    const bool odd = radix_passes(0, bits) % 2 == 1;
+    uint32_t* vin = at<uint32_t>(binning, odd ? BL.slot_g : BL.point_g);
+    uint32_t* valt = at<uint32_t>(binning, odd ? BL.point_g : BL.slot_g);
+    // the bin sort's superblock sums are zeroed by k_duplicate_bins (no memset launch)
+    size_t bs_off = 0;
+    const size_t bs_words = bshift ? sort_sup_words(NL, 0, bits, &bs_off) : 0;
+    ZeroJob zb{};
+    zb.p[0] = reinterpret_cast<float*>(at<uint32_t>(binning, BL.hist) + bs_off);
+    zb.n[0] = bs_words;
+    zb.count = bs_words ? 1 : 0;
+    { StageTimer T(kStDuplicate, s);
+    if (bshift) {
+      // (the backward's record flags live on the exact slots: zeroed here too)
+      // (capacity mode: pairs past the capacity are not written; exact-slot flags likewise)
+      const uint32_t cap = ndev ? (uint32_t)NL : 0xFFFFFFFFu;
+      STAGE(a, s, launch_duplicate_bins(a, f.geom, depth_order, bshift, at<uint8_t>(binning, BL.flag),
+                                        at<uint32_t>(binning, BL.key), vin, true, zb, meta, s, cap, cap));
+    } else {
+      STAGE(a, s, launch_duplicate(a, f.geom, depth_order, (uint32_t)a.P, at<uint32_t>(binning, BL.key), vin,
+                                   at<uint8_t>(binning, BL.flag), s));
+    } }
+    bool talt = false;
+    // a one-pass bin sort also hands back each bin's [start, end): into the
+    // tile_m region (16 B per tile; the forward render writes tile_m later)
+    uint2* bin_bounds = (bshift && (size_t)8 << bits <= (size_t)16 * f.grid.nt) ? tile_m : nullptr;
+    { StageTimer T(kStTileSort, s);
+    STAGE(a, s, radix_sort_pairs(at<uint32_t>(binning, BL.key), at<uint32_t>(binning, BL.key_alt), vin, valt, false,
+                                 NL, 0, bits, at<uint32_t>(binning, BL.hist), at<uint32_t>(binning, BL.totals), s,
+                                 &talt, bin_bounds, &bounds_done, bs_words != 0, ndev)); }
+    // the Gaussian ids are the payload; the backward recomputes each pair's
+    // record slot from (Gaussian, tile) instead of carrying it through the sort
+    if (talt != odd) return set_error(WGSR_EHIP, "internal: list sort parity");
+    // (only the sort's bounds know the live count: without them the kernels
+    // below would take all NL slots for pairs)
+    if (ndev && !bounds_done) return set_error(WGSR_EHIP, "internal: capacity mode without the sort's bin bounds");
+    sorted_keys = at<uint32_t>(binning, talt ? BL.key_alt : BL.key);
+    sorted_gid = at<uint32_t>(binning, BL.point_g);
+    emit = bin_depth && bds_emit(bshift);
+    if (bin_depth) {
+      // each bin by depth, into the spare key / payload buffers; scratch for
+      // bins beyond one LDS tile: the region behind the lists (>= 16 NL bytes)
+      // ... and with small bins (bds_emit) it emits the per-tile lists and
+      // ranges itself (no k_expand_bins)
+      StageTimer T(kStTileSort, s);
+      uint32_t* okeys = at<uint32_t>(binning, talt ? BL.key : BL.key_alt);
+      uint32_t* ogid = at<uint32_t>(binning, BL.slot_g);
+      // (it gathers its keys from the Gaussians' depth keys)
+      STAGE(a, s, launch_bin_depth_sort(a, sorted_keys, sorted_gid, (uint32_t)NL, bshift, tile_m, bounds_done,
+                                        at<uint32_t>(f.geom, f.GL.dkey), okeys, ogid,
+                                        at<char>(binning, BL.total + plan.lists_bytes), s, emit ? lists : nullptr,
+                                        ranges, tile_len, meta));
+      bounds_done = true;
+      if (!emit) {
+        sorted_keys = okeys;
+        sorted_gid = ogid;
+      }
+    }
+  }
+  { StageTimer T(kStRanges, s);
+  if (emit) {
+    // (lists and ranges written by the per-bin depth sort)
+  } else if (bshift && NL > 0) {
+    STAGE(a, s, launch_expand_bins(a, sorted_keys, sorted_gid, (uint32_t)NL, bshift, tile_m, bounds_done, lists,
+                                   ranges, tile_len, meta, s));
+  } else {  // the exact pairs' tile ranges; without pairs (sorted_keys null) every list is empty
+    STAGE(a, s, launch_ranges(sorted_keys, (uint32_t)NL, f.grid.nt, ranges, tile_len, meta, s));
+  } }
+  StageTimer T(kStRenderFwd, s);
+  STAGE(a, s, launch_render_fwd(a, ranges, lists, f.geom, f.out_color, f.out_depth, f.out_opacity,
+                                f.im<float>(f.IL.final_T), f.im<uint32_t>(f.IL.n_contrib), f.n_touched,
+                                f.im<uint32_t>(f.IL.tile_m), s));
+  return WGSR_OK;
+}
 
 }  // namespace
 }  // namespace wgsr
@@ -360,46 +685,16 @@ int wgsr_rasterize_forward(const wgsr_raster_args* args, wgsr_alloc_fn geom_allo
     HIPCHK(hipMemsetAsync(out_opacity, 0, HW * sizeof(float), s));
     return WGSR_OK;
   }
-  const Grid grid(a);
-  const GeomLayout GL((size_t)a.P);
-  const ImageLayout IL(a.W, a.H);
-  void* geom = call_alloc(geom_alloc, ctx, GL.total);
-  if (!geom) return set_error(WGSR_EALLOC, "geometry buffer allocation failed");
-  void* image = call_alloc(image_alloc, ctx, IL.total);
-  if (!image) return set_error(WGSR_EALLOC, "image buffer allocation failed");
-
+  Fwd f{a, s, Grid(a), GeomLayout((size_t)a.P), ImageLayout(a.W, a.H), bin_shift(a), out_color, out_depth, out_opacity,
+        n_touched};
+  if (int e = f.alloc(geom_alloc, image_alloc, ctx)) return e;
   // counter block (kCounterBytes): error flags and the partial sums of
   // upstream's num_rendered and of the exact list lengths, all produced by
   // k_preprocess
   DevCounters* dc = dev_counters(s);
-  uint32_t* counter = dc ? dc->buf + (size_t)dc->parity * (kCounterBytes / 4) : at<uint32_t>(geom, GL.counter);
-  if (!dc) HIPCHK(hipMemsetAsync(counter, 0, kCounterBytes, s));
-  const int bshift = bin_shift(a);
-  const Bins bins(grid.gx, grid.gy, bshift);
-  // the depth sort's superblock sums are zeroed by k_preprocess's workgroups
-  // (no memset launch), and so is the next forward's counter block
-  bool bin_depth = depth_sort_bins(a, bshift);
-  const bool full_depth = !bin_depth && depth_sort_full();
-  size_t sup_off = 0;
-  const size_t sup_words = bin_depth    ? 0
-                           : full_depth ? sort_sup_words((size_t)a.P, 0, kDepthBits, &sup_off)
-                                        : depth_sort_sup_words((size_t)a.P);
-  if (!full_depth) sup_off = depth_sort_sup_offset_words((size_t)a.P);
-  ZeroJob zj{};
-  if (dc) {
-    zj.p[zj.count] = reinterpret_cast<float*>(dc->buf + (size_t)(dc->parity ^ 1) * (kCounterBytes / 4));
-    zj.n[zj.count++] = kCounterBytes / 4;
-  }
-  if (sup_words) {
-    zj.p[zj.count] = reinterpret_cast<float*>(at<uint32_t>(geom, GL.hist) + sup_off);
-    zj.n[zj.count++] = sup_words;
-  }
-  // ... and, with sort bins, the dual scan's superblock sums
-  const bool scan_sup = bshift != 0;
-  if (scan_sup) {
-    zj.p[zj.count] = at<float>(geom, GL.bsup);
-    zj.n[zj.count++] = 2 * kScanSupStride * packed_scan_supers((size_t)a.P);
-  }
+  f.counter = dc ? dc->buf + (size_t)dc->parity * (kCounterBytes / 4) : at<uint32_t>(f.geom, f.GL.counter);
+  if (!dc) HIPCHK(hipMemsetAsync(f.counter, 0, kCounterBytes, s));
+  const DepthSched sched = depth_schedule(f.bshift);
   // Once k_preprocess is queued it zeroes the thread's other counter block;
   // the next forward may only reuse that block after this call's host wait.
   // Any error return before that wait synchronises the stream instead.
@@ -408,303 +703,66 @@ int wgsr_rasterize_forward(const wgsr_raster_args* args, wgsr_alloc_fn geom_allo
     bool armed = false;
     ~SyncOnError() { if (armed) (void)hipStreamSynchronize(s); }
   } sync_on_error{s};
-  { StageTimer T(0, s);
-  const hipError_t pe = launch_preprocess(a, geom, radii, n_touched, counter + 1,
-                                          reinterpret_cast<unsigned long long*>(counter + 4), bshift, zj, s,
-                                          at<uint32_t>(image, IL.meta));
+  { StageTimer T(kStPreprocess, s);
+  const hipError_t pe = launch_preprocess(a, f.geom, radii, n_touched, f.counter + 1,
+                                          reinterpret_cast<unsigned long long*>(f.counter + 4), f.bshift,
+                                          preprocess_zero_job(f, dc, sched), s, f.im<uint32_t>(f.IL.meta));
   if (pe == hipSuccess && dc) dc->parity ^= 1;  // k_preprocess, which zeroes the other block, is queued
   sync_on_error.armed = true;
   STAGE(a, s, pe); }
 
-  // The pair counts are known once k_preprocess is done: copy them to pinned
-  // host memory behind it and let the depth sort + scan run while the host
-  // waits for them, allocates the binning buffer and queues the rest.
   HostCounters& hc = host_counters();
-  if (!hc.buf || !hc.ev) return set_error(WGSR_EHIP, "pinned counter buffer / event allocation failed");
-  // (with the per-bin depth sort nothing would overlap the copy on the side
-  // stream, whose start waits out an event round trip: copy in stream order)
-  // per-bin default: the scan's first wave publishes the counts (PublishJob)
-  const bool mailbox = bin_depth && bshift && hc.mbox;
-  // (24-bit sequence numbers, never 0: the record's initial value)
-  const uint32_t want = mailbox ? (hc.seq = (hc.seq % 0xFFFFFFu) + 1u) : 0u;
   PublishJob pub{};
-  if (mailbox) {
-    // (no event behind it: an event record makes the runtime end the kernel
-    // with a system-scope release, ~6 us before the next kernel starts; the
-    // wait below checks the stream itself instead)
-    pub.counter = counter;
-    pub.host = hc.mbox;
-    pub.seq = want;
-  } else if (hc.side && !bin_depth) {
-    HIPCHK(hipEventRecord(hc.pre, s));
-    HIPCHK(hipStreamWaitEvent(hc.side, hc.pre, 0));
-    HIPCHK(hipMemcpyAsync(hc.buf, counter, kCounterBytes, hipMemcpyDeviceToHost, hc.side));
-    HIPCHK(hipEventRecord(hc.ev, hc.side));
-  } else {
-    HIPCHK(hipMemcpyAsync(hc.buf, counter, kCounterBytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipEventRecord(hc.ev, s));
-  }
-  // depth order of the Gaussians (culled ones carry key 0xFFFFFFFF -> last)
-  const uint32_t* depth_order = nullptr;  // null: index order (bin_depth)
-  if (!bin_depth) { StageTimer T(1, s);
-  if (full_depth) {
-    bool in_alt = false;
-    STAGE(a, s, radix_sort_pairs(at<uint32_t>(geom, GL.dkey), at<uint32_t>(geom, GL.dkey_alt),
-                                 at<uint32_t>(geom, GL.dval), at<uint32_t>(geom, GL.dval_alt), true, (size_t)a.P, 0,
-                                 kDepthBits, at<uint32_t>(geom, GL.hist), at<uint32_t>(geom, GL.totals), s, &in_alt,
-                                 nullptr, nullptr, sup_words != 0));
-    if (in_alt != kFullDepthInAlt) return set_error(WGSR_EHIP, "internal: depth sort parity");
-    depth_order = at<uint32_t>(geom, kFullDepthInAlt ? GL.dval_alt : GL.dval);
-  } else {
-    STAGE(a, s, launch_depth_sort(at<uint32_t>(geom, GL.dkey), at<uint32_t>(geom, GL.dkey_alt),
-                                  at<uint32_t>(geom, GL.dval), at<uint32_t>(geom, GL.dval_alt), (size_t)a.P,
-                                  counter + kDepthRangeOffset / 4, counter + 2, at<uint32_t>(geom, GL.hist), s));
-    depth_order = at<uint32_t>(geom, GL.dval_alt);
-  } }
-  // in depth order: duplicate-slot offsets of the exact tile lists (the
-  // backward's record slots; Gaussian -> first slot), and with sort bins the
-  // bin-pair offsets -- their down-sweep writes the pairs, after the binning
-  // buffer exists
-  auto queue_scan = [&](const PublishJob& pj) -> int {
-    StageTimer T(2, s);
-    if (bshift) {  // block sums of (list length, bins) in depth order; k_duplicate_bins finishes the scan
-      STAGE(a, s, packed_scan_blocks(at<uint32_t>(geom, GL.tb), 1, depth_order, (size_t)a.P,
-                                     at<uint32_t>(geom, GL.bsum), s, scan_sup ? at<uint2>(geom, GL.bsup) : nullptr,
-                                     pj));
-    } else {
-      STAGE(a, s, exclusive_scan_gather(&at<ListRec>(geom, GL.lrec)->w.w, depth_order, (size_t)a.P,
-                                        at<uint32_t>(geom, GL.offs), at<uint32_t>(geom, GL.slot_start),
-                                        at<uint32_t>(geom, GL.bsum), at<uint32_t>(geom, GL.counter), s,
-                                        sizeof(ListRec) / 4));
-    }
-    return WGSR_OK;
-  };
-  if (int e = queue_scan(pub)) return e;
+  if (int e = start_counts_readback(f, sched == DepthSched::kBins, hc, &pub)) return e;
+  const uint32_t* depth_order = nullptr;  // null: index order (the per-bin depth sort)
+  if (sched != DepthSched::kBins)
+    if (int e = queue_depth_sort(f, sched == DepthSched::kFull, false, &depth_order)) return e;
+  if (int e = queue_scan(f, depth_order, pub)) return e;
   // the predicted binning buffer, allocated while the GPU works
   BinningGuess& bg = binning_guess();
   void* binning = nullptr;
   size_t binning_have = 0;
-  if (bg.P == a.P && bg.W == a.W && bg.H == a.H && bg.bshift == bshift && bg.bytes > 0) {
+  if (bg.P == a.P && bg.W == a.W && bg.H == a.H && bg.bshift == f.bshift && bg.bytes > 0) {
     binning_have = bg.bytes + bg.bytes / 16;
     binning = call_alloc(binning_alloc, ctx, binning_have);
     if (!binning) binning_have = 0;
   }
-  const uint32_t* host_counter = hc.buf;
-  uint4 rec = make_uint4(0u, 0u, 0u, 0u);
-  bool published_ok = true;
-  if (mailbox) {
-    // spin on the published word; every 1024 polls the stream is checked,
-    // so a failed stream ends the wait (and a publish that never became
-    // visible falls back to a copy)
-    // (one aligned 16-byte load: the record is written by one 16-byte store)
-    auto poll = [&]() {
-      asm volatile("" ::: "memory");  // (a fresh load every poll: the GPU writes the record)
-      const __m128i v = _mm_load_si128(reinterpret_cast<const __m128i*>(const_cast<const uint4*>(hc.mbox)));
-      _mm_storeu_si128(reinterpret_cast<__m128i*>(&rec), v);
-      return (rec.x >> 8) == want;
-    };
-    uint32_t polls = 0;
-    while (!poll()) {
-      _mm_pause();
-      if ((++polls & 1023u) == 0) {
-        const hipError_t q = hipStreamQuery(s);
-        if (q == hipErrorNotReady) continue;
-        HIPCHK(q);
-        // the stream is done: the record may still be in flight to host
-        // memory (a posted write) -- a few more polls before giving up on it
-        bool seen = false;
-        for (int k = 0; k < (1 << 16) && !(seen = poll()); ++k) _mm_pause();
-        if (seen) break;
-        hc.mbox = nullptr;  // (not visible on this system: copies from now on)
-        break;
-      }
-    }
-    if (hc.mbox && (rec.x & 0x80u)) published_ok = false;  // a count beyond 32 bits: the block itself
-    if (!hc.mbox || !published_ok) {
-      HIPCHK(hipMemcpyAsync(hc.buf, counter, kCounterBytes, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipStreamSynchronize(s));
-    }
-  } else {
-    HIPCHK(hipEventSynchronize(hc.ev));
-  }
+  Counts c;
+  if (int e = wait_counts(f, hc, pub, &c)) return e;
   sync_on_error.armed = false;
-  // upstream num_rendered, exact (Gaussian, tile) pairs (<= N_rect), (Gaussian, bin) pairs
-  size_t N_rect = 0, N = 0, N_bin = 0;
-  uint32_t host_flags = 0;
-  const bool published = mailbox && hc.mbox && published_ok;
-  if (published) {
-    host_flags = rec.x & 0x7Fu;
-    N_rect = rec.y;
-    N = rec.z;
-    N_bin = rec.w;
-  } else {
-    const uint64_t* partial = reinterpret_cast<const uint64_t*>(host_counter + 4);
-    for (int i = 0; i < kRectPairLanes; ++i) {
-      N_rect += partial[i];
-      N += partial[kRectPairLanes + i];
-      N_bin += partial[2 * kRectPairLanes + i];
-    }
-    host_flags = host_counter[1];
-  }
-  if (bin_depth && N_bin > bin_depth_max_avg() * (size_t)bins.n) {
-    // bins too full for one LDS-resident sort each: the Gaussian-level depth
-    // sort after all (queued now, with its scratch zeroed and the scan redone
-    // in depth order)
-    bin_depth = false;
-    StageTimer T(1, s);
-    HIPCHK(hipMemsetAsync(at<uint32_t>(geom, GL.hist) + depth_sort_sup_offset_words((size_t)a.P), 0,
-                          4 * depth_sort_sup_words((size_t)a.P), s));
-    STAGE(a, s, launch_depth_sort(at<uint32_t>(geom, GL.dkey), at<uint32_t>(geom, GL.dkey_alt),
-                                  at<uint32_t>(geom, GL.dval), at<uint32_t>(geom, GL.dval_alt), (size_t)a.P,
-                                  counter + kDepthRangeOffset / 4, counter + 2, at<uint32_t>(geom, GL.hist), s));
-    depth_order = at<uint32_t>(geom, GL.dval_alt);
-    if (scan_sup)
-      HIPCHK(hipMemsetAsync(at<uint2>(geom, GL.bsup), 0,
-                            sizeof(uint2) * kScanSupStride * packed_scan_supers((size_t)a.P), s));
-    if (int e = queue_scan(PublishJob{})) return e;
-  }
-  if (!full_depth && !bin_depth) {
-    // depths spanning more than the three passes' bits: one more stable pass
-    // over the bits above them, then the scan again in the final order
-    // (the published counts carry no key range: the bins-too-full switch
-    // above reads the block, rarely)
-    if (published) {
-      HIPCHK(hipMemcpyAsync(hc.buf, counter, kCounterBytes, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipStreamSynchronize(s));
-    }
-    const uint32_t* rw = host_counter + kDepthRangeOffset / 4;
-    uint32_t hi = 0, nlo = 0;
-    for (int i = 0; i < kRectPairLanes; ++i) {
-      hi = rw[i] > hi ? rw[i] : hi;
-      nlo = rw[kRectPairLanes + i] > nlo ? rw[kRectPairLanes + i] : nlo;
-    }
-    const DepthKeyPlan pl = depth_key_plan(hi, ~nlo);
-    if (pl.extra_bits > 0) {
-      bool alt = false;
-      StageTimer T(1, s);
-      STAGE(a, s, radix_sort_pairs(at<uint32_t>(geom, GL.dkey_alt), at<uint32_t>(geom, GL.dkey),
-                                   at<uint32_t>(geom, GL.dval_alt), at<uint32_t>(geom, GL.dval), false, (size_t)a.P,
-                                   pl.extra_shift, pl.R, at<uint32_t>(geom, GL.hist), at<uint32_t>(geom, GL.totals),
-                                   s, &alt));
-      depth_order = at<uint32_t>(geom, alt ? GL.dval : GL.dval_alt);
-      if (scan_sup)
-        HIPCHK(hipMemsetAsync(at<uint2>(geom, GL.bsup), 0,
-                              sizeof(uint2) * kScanSupStride * packed_scan_supers((size_t)a.P), s));
-      if (int e = queue_scan(PublishJob{})) return e;
-    }
-  }
-  g_depth_order_off = depth_order ? (int64_t)(reinterpret_cast<const uint8_t*>(depth_order) -
-                                              static_cast<const uint8_t*>(geom))
-                                  : (int64_t)-1;
-  if (host_flags && a.prefiltered)
-    return set_error(WGSR_EINVAL, "Error: a prefiltered Gaussian lies behind the near plane");
-  if (N > N_rect) return set_error(WGSR_EHIP, "internal: exact tile lists exceed the rectangles");
-  if (N_bin > N_rect) return set_error(WGSR_EHIP, "internal: bin pairs exceed the rectangles");
 
-  // the binning layout is sized by upstream's num_rendered (returned to the
-  // caller and handed back to the backward), so both sides agree on it; with
-  // sort bins the per-tile lists follow it (2^2s entries per bin pair)
-  const BinLayout BL(N_rect);
-  const size_t lists_bytes = bshift ? align256(4 * ((size_t)N_bin << (2 * bshift))) : 0;
-  // per-bin depth sort: scratch of the bins beyond one LDS tile (two uint2
-  // ping-pong arrays; not the list region, which the same kernel now writes)
-  const size_t bds_bytes = bin_depth ? align256(16 * (size_t)N_bin) : 0;
-  const size_t binning_bytes = BL.total + lists_bytes + bds_bytes;
-  bg.P = a.P; bg.W = a.W; bg.H = a.H; bg.bshift = bshift; bg.bytes = binning_bytes;
+  // bins too full for one LDS-resident sort each: the Gaussian-level depth
+  // sort after all (queued now, with its scratch zeroed and the scan redone
+  // in depth order)
+  const bool bins_too_full = sched == DepthSched::kBins &&
+                             c.N_bin > bin_depth_max_avg() * (size_t)Bins(f.grid.gx, f.grid.gy, f.bshift).n;
+  if (bins_too_full) {
+    if (int e = queue_depth_sort(f, false, true, &depth_order)) return e;
+    if (int e = requeue_scan(f, depth_order)) return e;
+  }
+  if (sched == DepthSched::kGlobal || bins_too_full)
+    if (int e = queue_depth_fixup(f, hc, c, &depth_order)) return e;
+  const bool bin_depth = sched == DepthSched::kBins && !bins_too_full;
+  g_depth_order_off =
+      depth_order ? (int64_t)(reinterpret_cast<const uint8_t*>(depth_order) - f.g<const uint8_t>(0)) : (int64_t)-1;
+  if (c.flags && a.prefiltered)
+    return set_error(WGSR_EINVAL, "Error: a prefiltered Gaussian lies behind the near plane");
+  if (c.N > c.N_rect) return set_error(WGSR_EHIP, "internal: exact tile lists exceed the rectangles");
+  if (c.N_bin > c.N_rect) return set_error(WGSR_EHIP, "internal: bin pairs exceed the rectangles");
+
+  const BinningPlan plan(c.N_rect, c.N_bin, f.bshift, bin_depth);
+  bg.P = a.P; bg.W = a.W; bg.H = a.H; bg.bshift = f.bshift; bg.bytes = plan.total;
   // the exact size is allocated only without (or beyond) a prediction; a
   // predicted buffer that is large enough is used as it is (the layout only
-  // needs binning_bytes of it), so a callback is never asked twice for a
+  // needs plan.total of it), so a callback is never asked twice for a
   // buffer it has to keep
-  if (binning_bytes > binning_have) {
-    binning = call_alloc(binning_alloc, ctx, binning_bytes);
-    if (!binning && binning_bytes) return set_error(WGSR_EALLOC, "binning buffer allocation failed");
+  if (plan.total > binning_have) {
+    binning = call_alloc(binning_alloc, ctx, plan.total);
+    if (!binning && plan.total) return set_error(WGSR_EALLOC, "binning buffer allocation failed");
   }
-  uint32_t* lists = bshift ? at<uint32_t>(binning, BL.total) : at<uint32_t>(binning, BL.point_g);
-  // (the per-bin depth sort gathers its keys from the Gaussians' depth keys)
-  const uint32_t* gdep = bin_depth ? at<uint32_t>(geom, GeomLayout((size_t)a.P).dkey) : nullptr;
-  void* bds_scratch = bin_depth ? static_cast<void*>(at<char>(binning, BL.total + lists_bytes)) : nullptr;
-  uint2* ranges = at<uint2>(image, IL.ranges);
-  // sorted pairs: (Gaussian, bin) pairs, or with bin shift 0 the exact
-  // (Gaussian, tile) pairs themselves
-  const size_t NL = bshift ? N_bin : N;
-  if (NL > 0) {
-    const int bits = bshift ? (num_bits((uint32_t)bins.n) > 0 ? num_bits((uint32_t)bins.n) : 1) : tile_sort_bits(grid);
-    // the LSD sort alternates buffers every pass: start the payload in the
-    // buffer that makes it end in point_g
-    const bool odd = radix_passes(0, bits) % 2 == 1;
-    uint32_t* vin = at<uint32_t>(binning, odd ? BL.slot_g : BL.point_g);
-    uint32_t* valt = at<uint32_t>(binning, odd ? BL.point_g : BL.slot_g);
-    // the bin sort's superblock sums are zeroed by k_duplicate_bins (no memset launch)
-    size_t bs_off = 0;
-    const size_t bs_words = bshift ? sort_sup_words(NL, 0, bits, &bs_off) : 0;
-    ZeroJob zb{};
-    if (bs_words) {
-      zb.p[0] = reinterpret_cast<float*>(at<uint32_t>(binning, BL.hist) + bs_off);
-      zb.n[0] = bs_words;
-      zb.count = 1;
-    }
-    { StageTimer T(3, s);
-    if (bshift) {
-      // (the backward's record flags live on the exact slots: zeroed here too)
-      STAGE(a, s, launch_duplicate_bins(a, geom, depth_order, bshift, at<uint8_t>(binning, BL.flag),
-                                        at<uint32_t>(binning, BL.key), vin, scan_sup, zb,
-                                        at<uint32_t>(image, IL.meta), s));
-    } else {
-      STAGE(a, s, launch_duplicate(a, geom, depth_order, (uint32_t)a.P, at<uint32_t>(binning, BL.key), vin,
-                                   at<uint8_t>(binning, BL.flag), s));
-    } }
-    bool talt = false, bounds_done = false;
-    // a one-pass bin sort also hands back each bin's [start, end): into the
-    // tile_m region (16 B per tile; the forward render writes tile_m later)
-    uint2* bin_bounds = (bshift && (size_t)8 << bits <= (size_t)16 * grid.nt) ? at<uint2>(image, IL.tile_m) : nullptr;
-    { StageTimer T(4, s);
-    STAGE(a, s, radix_sort_pairs(at<uint32_t>(binning, BL.key), at<uint32_t>(binning, BL.key_alt), vin, valt, false,
-                                 NL, 0, bits, at<uint32_t>(binning, BL.hist), at<uint32_t>(binning, BL.totals), s,
-                                 &talt, bin_bounds, &bounds_done, bs_words != 0)); }
-    // the Gaussian ids are the payload; the backward recomputes each pair's
-    // record slot from (Gaussian, tile) instead of carrying it through the sort
-    if (talt != odd) return set_error(WGSR_EHIP, "internal: list sort parity");
-    const uint32_t* sorted_keys = at<uint32_t>(binning, talt ? BL.key_alt : BL.key);
-    const uint32_t* sorted_gid = at<uint32_t>(binning, BL.point_g);
-    if (bin_depth) {
-      // each bin by depth, into the spare key / payload buffers; scratch for
-      // bins beyond one LDS tile: the list region (>= 16 NL bytes)
-      // ... and emits the per-tile lists and ranges itself (no k_expand_bins)
-      StageTimer T(4, s);
-      uint32_t* okeys = at<uint32_t>(binning, talt ? BL.key : BL.key_alt);
-      uint32_t* ogid = at<uint32_t>(binning, BL.slot_g);
-      const bool emit = bds_emit(bshift);
-      STAGE(a, s, launch_bin_depth_sort(a, sorted_keys, sorted_gid, (uint32_t)NL, bshift, at<uint2>(image, IL.tile_m),
-                                        bounds_done, gdep, okeys, ogid, bds_scratch, s, emit ? lists : nullptr,
-                                        ranges, at<uint32_t>(image, IL.tile_len), at<uint32_t>(image, IL.meta)));
-      bounds_done = true;
-      if (!emit) {
-        sorted_keys = okeys;
-        sorted_gid = ogid;
-      }
-    }
-    StageTimer T(5, s);
-    if (bin_depth && bds_emit(bshift)) {
-      // (lists and ranges written by the per-bin depth sort)
-    } else if (bshift) {
-      STAGE(a, s, launch_expand_bins(a, sorted_keys, sorted_gid, (uint32_t)NL, bshift,
-                                     at<uint2>(image, IL.tile_m), bounds_done, lists, ranges,
-                                     at<uint32_t>(image, IL.tile_len), at<uint32_t>(image, IL.meta), s));
-    } else {
-      STAGE(a, s, launch_ranges(sorted_keys, (uint32_t)NL, grid.nt, ranges, at<uint32_t>(image, IL.tile_len),
-                                at<uint32_t>(image, IL.meta), s));
-    }
-  } else {
-    StageTimer T(5, s);  // every list is empty
-    STAGE(a, s, launch_ranges(nullptr, 0u, grid.nt, ranges, at<uint32_t>(image, IL.tile_len),
-                              at<uint32_t>(image, IL.meta), s));
-  }
-  const uint32_t* sorted_g = lists;
-  { StageTimer T(6, s);
-  STAGE(a, s, launch_render_fwd(a, ranges, sorted_g, geom,
-                                out_color, out_depth, out_opacity, at<float>(image, IL.final_T),
-                                at<uint32_t>(image, IL.n_contrib), n_touched, at<uint32_t>(image, IL.tile_m), s)); }
-  *num_rendered = (int64_t)N_rect;
+  if (int e = queue_lists_and_render(f, binning, plan, depth_order, bin_depth, f.bshift ? c.N_bin : c.N, nullptr))
+    return e;
+  *num_rendered = (int64_t)c.N_rect;
   return WGSR_OK;
 }
 
@@ -722,9 +780,7 @@ int wgsr_check_tile_lists(const wgsr_raster_args* args, int64_t num_rendered, co
 
 size_t wgsr_binning_bytes_cap(const wgsr_raster_args* args, int64_t cap) {
   if (!args || cap < 0) return 0;
-  const int bshift = bin_shift(*args);
-  const size_t C = (size_t)cap;
-  return BinLayout(C).total + align256(4 * (C << (2 * bshift))) + align256(16 * C);
+  return BinningPlan((size_t)cap, (size_t)cap, bin_shift(*args), true).total;
 }
 
 // Capacity mode (wgsr.h): the forward above without its one host wait.  The
@@ -762,90 +818,33 @@ int wgsr_rasterize_forward_cap(const wgsr_raster_args* args, int64_t cap, wgsr_a
     HIPCHK(launch_zero_u32(counts, 5, s));
     return WGSR_OK;
   }
-  const Grid grid(a);
-  const int bshift = bin_shift(a);
-  if (!bshift || !depth_sort_bins(a, bshift))
+  Fwd f{a, s, Grid(a), GeomLayout((size_t)a.P), ImageLayout(a.W, a.H), bin_shift(a), out_color, out_depth, out_opacity,
+        n_touched};
+  if (!f.bshift || depth_schedule(f.bshift) != DepthSched::kBins)
     return set_error(WGSR_EINVAL, "capacity mode needs sort bins with the per-bin depth sort");
-  const Bins bins(grid.gx, grid.gy, bshift);
-  const int bits = num_bits((uint32_t)bins.n) > 0 ? num_bits((uint32_t)bins.n) : 1;
-  if (!((size_t)8 << bits <= (size_t)16 * grid.nt))
+  if (!((size_t)8 << sort_bits(Bins(f.grid.gx, f.grid.gy, f.bshift).n) <= (size_t)16 * f.grid.nt))
     return set_error(WGSR_EINVAL, "capacity mode: the bin bounds do not fit the tile_m region");
-  const GeomLayout GL((size_t)a.P);
-  const ImageLayout IL(a.W, a.H);
-  void* geom = call_alloc(geom_alloc, ctx, GL.total);
-  if (!geom) return set_error(WGSR_EALLOC, "geometry buffer allocation failed");
-  void* image = call_alloc(image_alloc, ctx, IL.total);
-  if (!image) return set_error(WGSR_EALLOC, "image buffer allocation failed");
+  if (int e = f.alloc(geom_alloc, image_alloc, ctx)) return e;
   const size_t C = (size_t)cap;
-  const BinLayout BL(C);
-  const size_t lists_bytes = align256(4 * (C << (2 * bshift)));
-  const size_t binning_bytes = BL.total + lists_bytes + align256(16 * C);
-  void* binning = call_alloc(binning_alloc, ctx, binning_bytes);
+  const BinningPlan plan(C, C, f.bshift, true);
+  void* binning = call_alloc(binning_alloc, ctx, plan.total);
   if (!binning) return set_error(WGSR_EALLOC, "binning buffer allocation failed");
-  uint32_t* lists = at<uint32_t>(binning, BL.total);
-  const uint32_t* gdep = at<uint32_t>(geom, GL.dkey);
-  void* bds_scratch = at<char>(binning, BL.total + lists_bytes);
-  uint32_t* counter = at<uint32_t>(geom, GL.counter);
-  uint32_t* meta = at<uint32_t>(image, IL.meta);
+  f.counter = at<uint32_t>(f.geom, f.GL.counter);
+  uint32_t* meta = at<uint32_t>(f.image, f.IL.meta);
   // the counter block zeroed by a kernel node (a captured memset node did not
   // reliably zero it: launch_zero_u32)
-  HIPCHK(launch_zero_u32(counter, kCounterBytes / 4, s));
-  ZeroJob zj{};
-  const bool scan_sup = true;
-  if (scan_sup) {
-    zj.p[zj.count] = at<float>(geom, GL.bsup);
-    zj.n[zj.count++] = 2 * kScanSupStride * packed_scan_supers((size_t)a.P);
-  }
-  { StageTimer T(0, s);
-  STAGE(a, s, launch_preprocess(a, geom, radii, n_touched, counter + 1,
-                                reinterpret_cast<unsigned long long*>(counter + 4), bshift, zj, s, meta)); }
-  STAGE(a, s, launch_cap_counts(reinterpret_cast<const unsigned long long*>(counter + 4), (uint64_t)C, (uint64_t)C,
+  HIPCHK(launch_zero_u32(f.counter, kCounterBytes / 4, s));
+  const ZeroJob zj = preprocess_zero_job(f, nullptr, DepthSched::kBins);  // (the dual scan's superblock sums)
+  { StageTimer T(kStPreprocess, s);
+  STAGE(a, s, launch_preprocess(a, f.geom, radii, n_touched, f.counter + 1,
+                                reinterpret_cast<unsigned long long*>(f.counter + 4), f.bshift, zj, s, meta)); }
+  STAGE(a, s, launch_cap_counts(reinterpret_cast<const unsigned long long*>(f.counter + 4), (uint64_t)C, (uint64_t)C,
                                 counts, meta, s));
-  { StageTimer T(2, s);  // block sums of (list length, bins) in index order
-  STAGE(a, s, packed_scan_blocks(at<uint32_t>(geom, GL.tb), 1, nullptr, (size_t)a.P, at<uint32_t>(geom, GL.bsum), s,
-                                 scan_sup ? at<uint2>(geom, GL.bsup) : nullptr)); }
-  const bool odd = radix_passes(0, bits) % 2 == 1;
-  uint32_t* vin = at<uint32_t>(binning, odd ? BL.slot_g : BL.point_g);
-  uint32_t* valt = at<uint32_t>(binning, odd ? BL.point_g : BL.slot_g);
-  size_t bs_off = 0;
-  const size_t bs_words = sort_sup_words(C, 0, bits, &bs_off);
-  ZeroJob zb{};
-  if (bs_words) {
-    zb.p[0] = reinterpret_cast<float*>(at<uint32_t>(binning, BL.hist) + bs_off);
-    zb.n[0] = bs_words;
-    zb.count = 1;
-  }
-  { StageTimer T(3, s);  // (pairs past the capacity are not written; exact-slot flags likewise)
-  STAGE(a, s, launch_duplicate_bins(a, geom, nullptr, bshift, at<uint8_t>(binning, BL.flag),
-                                    at<uint32_t>(binning, BL.key), vin, scan_sup, zb, at<uint32_t>(image, IL.meta), s,
-                                    (uint32_t)C, (uint32_t)C)); }
-  bool talt = false, bounds_done = false;
-  uint2* bin_bounds = at<uint2>(image, IL.tile_m);
-  { StageTimer T(4, s);
-  STAGE(a, s, radix_sort_pairs(at<uint32_t>(binning, BL.key), at<uint32_t>(binning, BL.key_alt), vin, valt, false, C,
-                               0, bits, at<uint32_t>(binning, BL.hist), at<uint32_t>(binning, BL.totals), s, &talt,
-                               bin_bounds, &bounds_done, bs_words != 0, counts + 4)); }
-  if (talt != odd) return set_error(WGSR_EHIP, "internal: list sort parity");
-  if (!bounds_done) return set_error(WGSR_EHIP, "internal: capacity mode without the sort's bin bounds");
-  const uint32_t* sorted_keys = at<uint32_t>(binning, talt ? BL.key_alt : BL.key);
-  const uint32_t* sorted_gid = at<uint32_t>(binning, BL.point_g);
-  uint2* ranges = at<uint2>(image, IL.ranges);
-  const bool emit = bds_emit(bshift);
-  uint32_t* okeys = at<uint32_t>(binning, talt ? BL.key : BL.key_alt);
-  uint32_t* ogid = at<uint32_t>(binning, BL.slot_g);
-  { StageTimer T(4, s);
-  STAGE(a, s, launch_bin_depth_sort(a, sorted_keys, sorted_gid, (uint32_t)C, bshift, bin_bounds, true, gdep, okeys,
-                                    ogid, bds_scratch, s, emit ? lists : nullptr, ranges,
-                                    at<uint32_t>(image, IL.tile_len), meta)); }
-  if (!emit) { StageTimer T(5, s);
-    STAGE(a, s, launch_expand_bins(a, okeys, ogid, (uint32_t)C, bshift, bin_bounds, true, lists, ranges,
-                                   at<uint32_t>(image, IL.tile_len), meta, s));
-  }
+  // block sums of (list length, bins) in index order
+  if (int e = queue_scan(f, nullptr, PublishJob{})) return e;
   g_depth_order_off = -1;
-  { StageTimer T(6, s);
-  STAGE(a, s, launch_render_fwd(a, ranges, lists, geom, out_color, out_depth, out_opacity, at<float>(image, IL.final_T),
-                                at<uint32_t>(image, IL.n_contrib), n_touched, at<uint32_t>(image, IL.tile_m), s)); }
-  return WGSR_OK;
+  // the bin sort reads its key count from counts[4] and hands back the bin bounds
+  return queue_lists_and_render(f, binning, plan, nullptr, true, C, counts + 4);
 }
 
 }  // extern "C"
@@ -875,7 +874,7 @@ int render_backward_pairs(const wgsr_raster_args& a, const void* geom, void* bin
   const BinLayout BL(N);
   uint8_t* pflag = N > 0 ? at<uint8_t>(binning, BL.flag) : nullptr;
   if (N > 0) {
-    StageTimer T(7, s);
+    StageTimer T(kStRenderBwd, s);
     uint32_t* order = at<uint32_t>(image, IL.order_bwd);
     STAGE(a, s, launch_tile_order(at<uint32_t>(image, IL.tile_m), grid.nt, order, s));
     // the tile lists: point_g, or with sort bins the region after the sized
@@ -927,7 +926,7 @@ int wgsr_rasterize_backward(const wgsr_raster_args* args, const int32_t* radii, 
   if (int e = render_backward_pairs(a, geom, binning, image, num_rendered, dL_dcolor, dL_ddepth, scratch_alloc, ctx,
                                     zero, s, &partial, &pflag))
     return e;
-  StageTimer T(8, s);
+  StageTimer T(kStGaussBwd, s);
   STAGE(a, s, launch_gauss_bwd(a, geom, partial, pflag, at<uint32_t>(image, ImageLayout(a.W, a.H).meta), dL_dmeans2D, dL_dcolors, dL_dopacity, dL_dmeans3D, dL_dcov3D,
                                dL_dsh, dL_dscales, dL_drotations, dL_dtau, s));
   return WGSR_OK;
@@ -958,7 +957,7 @@ int wgsr_rasterize_backward_records(const wgsr_raster_args* args, const int32_t*
                                       ctx, ZeroJob{}, s, &partial, &pflag))
       return e;
   }
-  StageTimer T(8, s);
+  StageTimer T(kStGaussBwd, s);
   STAGE(a, s, launch_view_records(a, radii, geom, partial, pflag, P_pad, records, s));
   return WGSR_OK;
 }
@@ -990,7 +989,7 @@ int wgsr_gauss_backward_views(const wgsr_raster_args* params, int lo, int hi, in
   if (!dL_dmeans3D || !dL_dopacity || !dL_dscales || !dL_drotations || (a.shs && !dL_dsh))
     return set_error(WGSR_EINVAL, "missing gradient output");
   hipStream_t s = (hipStream_t)stream;
-  StageTimer T(8, s);
+  StageTimer T(kStGaussBwd, s);
   HIPCHK(launch_gauss_bwd_views(a, lo, hi, n_views, cameras, records, record_view_stride, dL_dmeans3D, dL_dsh,
                                 dL_dopacity, dL_dscales, dL_drotations, tau_partials, stats, s));
   if (a.debug) {
@@ -1014,7 +1013,7 @@ int wgsr_dist_cuda2(int P, const float* points, float* out, wgsr_alloc_fn scratc
   if (P == 0) return WGSR_OK;
   void* scratch = call_alloc(scratch_alloc, ctx, knn_scratch_bytes(P));
   if (!scratch) return set_error(WGSR_EALLOC, "distCUDA2 scratch allocation failed");
-  StageTimer T(9, (hipStream_t)stream);
+  StageTimer T(kStDistCuda2, (hipStream_t)stream);
   HIPCHK(launch_dist_cuda2(P, points, out, scratch, (hipStream_t)stream));
   return WGSR_OK;
 }

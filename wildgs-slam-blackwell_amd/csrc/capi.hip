@@ -108,11 +108,15 @@ struct DevCounters {
   int parity = 0;
   bool failed = false;
 };
-// The per-bin depth sort emits the per-tile lists itself for small bins
-// (2 x 2 tiles: TUM 512 x 384, 35.4 -> 33.8 us for sort + lists); with 4 x 4-
-// tile bins (1080p) the 16-tile compaction inside the one-workgroup-per-CU
-// sort costs more than k_expand_bins' 4x wider grid (140.8 vs 131.3 us).
-bool bds_emit(int bshift) { return bshift <= 1; }
+// The per-bin depth sort emits the per-tile lists itself at every bin shift
+// (bds_emit_walk, raster_fwd.hip: each wave walks the sorted bin once for the
+// tiles it owns).  4 x 4-tile bins, 1M / 1080p: k_bin_depth_sort 39.5 -> 50.1
+// us with k_expand_bins' 29.5 us and its launch gone, 0.7473 -> 0.7325 ms per
+// step; 2 x 2-tile bins (100k 512 x 384, the online loop): 0.1672 -> 0.1665
+// and 0.7223 -> 0.7199 ms.  The earlier lane <-> entry emit
+// (a count pass, a prefix over the waves, a write pass) lost to k_expand_bins
+// at 4 x 4 tiles (140.8 vs 131.3 us) and is gone.
+bool bds_emit(int bshift) { return bshift >= 1 && bshift <= kMaxBinShift; }
 
 DevCounters* dev_counters(hipStream_t s) {
   thread_local DevCounters per_dev[kMaxDevices];
@@ -587,10 +591,10 @@ int queue_lists_and_render(const Fwd& f, void* binning, const BinningPlan& plan,
     sorted_gid = at<uint32_t>(binning, BL.point_g);
     emit = bin_depth && bds_emit(bshift);
     if (bin_depth) {
-      // each bin by depth, into the spare key / payload buffers; scratch for
-      // bins beyond one LDS tile: the region behind the lists (>= 16 NL bytes)
-      // ... and with small bins (bds_emit) it emits the per-tile lists and
-      // ranges itself (no k_expand_bins)
+      // each bin by depth; scratch for bins beyond one LDS tile: the region
+      // behind the lists (>= 16 NL bytes).  With bds_emit it writes the
+      // per-tile lists and ranges itself (no k_expand_bins); else the sorted
+      // bins go to the spare key / payload buffers
       StageTimer T(kStTileSort, s);
       uint32_t* okeys = at<uint32_t>(binning, talt ? BL.key : BL.key_alt);
       uint32_t* ogid = at<uint32_t>(binning, BL.slot_g);

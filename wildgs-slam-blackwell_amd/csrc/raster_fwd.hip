@@ -832,10 +832,11 @@ __global__ __launch_bounds__(kExpThreads) void k_expand_bins(const uint32_t* __r
 // order.  One 512-thread workgroup per bin: the bin's depth
 // keys minus their minimum (R bits) are LSD-radix sorted in LDS, ceil(R / 9)
 // stable passes of <= 9-bit digits, each entry's position in the bin riding
-// along; the (key, Gaussian) pairs are then gathered in that order into the
-// spare key / payload buffers.  A bin of more than kBdsCap entries runs the
-// same passes chunk by chunk through global scratch (the sort-bin list
-// region, free until k_expand_bins writes it).
+// along; the (key, Gaussian) pairs are then gathered in that order and cut
+// into the bin's per-tile lists (BdsEmit below; without it they go to the
+// spare key / payload buffers for k_expand_bins).  A bin of more than kBdsCap
+// entries runs the same passes chunk by chunk through global scratch (the
+// region behind the lists).
 // (512 threads, up to 10 entries per lane in steps of one: 1024 threads with
 // 1, 2, 4, 7 entries per lane measured 42-46 vs 33 us at 1M / 1080p)
 constexpr int kBdsThreads = 512, kBdsWaves = kBdsThreads / 64, kBdsItems = 10;
@@ -863,18 +864,28 @@ struct BdsLds {
   uint32_t base[kBdsDigits];              // per digit: first slot
   uint32_t tmp[kBdsWaves];
   uint32_t rng[2][kBdsWaves];
-  uint32_t etot[kBdsWaves][16];           // emit: per-wave entries per tile of the bin
-  uint32_t erun[16];                      // emit: entries per tile emitted so far
+  uint32_t ecnt[16];                      // emit: entries per tile of the bin, written by the tile's wave
 };
 
 // The bin's exact per-tile lists, emitted straight from the depth-sorted bin
 // (what k_expand_bins does from a global copy of it): tile k = r 2^s + c of
 // the bin gets, in depth order, every entry whose key has bit 16 + k set, at
 // lists[2^2s lo + k n + ...] (n = the bin's length: no count pass, no
-// overlap).  One chunk: wave w's lanes hold sorted positions (w JN + j) 64 +
-// lane of it in m[j] (the tile mask, 0 if none) and g[j] (the Gaussian);
-// per-wave counts per tile first, their prefix over the waves, then a
-// stable per-tile compaction (one ballot per (entry group, tile)).
+// overlap).  The walk is wave <-> tile: a chunk's sorted (tile mask, Gaussian)
+// pairs are staged once into L.buf (free after the last pass), and after one
+// barrier every wave walks the staged list 64 entries at a time for the
+// tiles it owns -- per step one 64-bit LDS read shared by its tiles, and per
+// tile a bit test, a ballot, a scalar popcount and one store at k n + running
+// count + lanes below.  A wave owns its tiles' whole lists, so there is no
+// count pass, no prefix over the waves and no barrier inside the walk; the
+// running counts are wave-uniform and carry across the chunks of a big bin.
+//   16 tiles (s = 2): wave w owns tiles w and w + 8.
+//    4 tiles (s = 1): waves w and w + 4 share tile w: both walk the whole
+//      chunk and count every hit (so both hold the tile's running count with
+//      no exchange), w stores the first half of the 64-entry groups and w + 4
+//      the second.  Counting a group is the read, the ballot and the popcount
+//      -- a fraction of a storing step -- so all eight waves work and the
+//      longest chain is half the stores of one wave per tile.
 struct BdsEmit {
   uint32_t* __restrict__ lists;
   uint2* __restrict__ ranges;
@@ -883,48 +894,78 @@ struct BdsEmit {
   int gx, gy, bshift, gbx;
 };
 
+// TPW tiles per wave: 2 (16 tiles) or 1 (4 tiles, two waves per tile)
+template <int TPW>
+__device__ __forceinline__ void bds_emit_walk(BdsLds& L, uint32_t cnt, uint32_t* __restrict__ out, uint32_t n,
+                                              uint32_t (&run)[2]) {
+  static_assert(TPW == 1 || TPW == 2, "16 or 4 tiles over eight waves");
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t w = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));  // (an SGPR)
+  const uint32_t groups = (cnt + 63u) >> 6;
+  const uint32_t k0 = TPW == 2 ? w : (w & 3u);
+  uint32_t g0 = 0u, g1 = groups;  // the groups whose hits this wave stores
+  if (TPW == 1) {
+    const uint32_t h = (groups + 1u) >> 1;
+    if (w >> 2) g0 = h; else g1 = h;
+  }
+  // each tile's next free slot as a uniform pointer (advanced by scalar
+  // popcounts): a store is that base plus a 32-bit lane offset
+  uint32_t kbit[TPW];
+  uint32_t* dst[TPW];
+#pragma unroll
+  for (int i = 0; i < TPW; ++i) {
+    const uint32_t k = k0 + 8u * (uint32_t)i;
+    kbit[i] = 1u << k;
+    dst[i] = out + (size_t)k * n + run[i];
+  }
+  auto emit = [&](const uint2 e, uint32_t g) {
+    const bool st = TPW == 2 || (g >= g0 && g < g1);  // wave-uniform
+#pragma unroll
+    for (int i = 0; i < TPW; ++i) {
+      const bool bit = (e.x & kbit[i]) != 0u;
+      const uint64_t b = wave_ballot(bit);
+      if (st && bit) dst[i][lanes_below(b)] = e.y;
+      dst[i] += __popcll(b);
+    }
+  };
+  // two groups per trip, each group's read in flight over the other's stores
+  // (the group past cnt is staged with zero masks)
+  const uint2* src = L.buf + lane;
+  uint2 ea = src[0], eb;
+  uint32_t g = 0;
+  for (; g + 1u < groups; g += 2u) {
+    eb = src[(g + 1u) * 64u];
+    emit(ea, g);
+    if (g + 2u < groups) ea = src[(g + 2u) * 64u];
+    emit(eb, g + 1u);
+  }
+  if (g < groups) emit(ea, g);
+#pragma unroll
+  for (int i = 0; i < TPW; ++i) {
+    const uint32_t k = k0 + 8u * (uint32_t)i;
+    run[i] = (uint32_t)(dst[i] - (out + (size_t)k * n));
+    if (lane == 0u && (TPW == 2 || w < 4u)) L.ecnt[k] = run[i];  // (the last chunk's is the tile's length)
+  }
+}
+
+// One chunk: wave w's lanes hold sorted positions (w JN + j) 64 + lane of it
+// in m[j] (the tile mask, 0 past cnt) and g[j] (the Gaussian).  run: the
+// wave's tiles' entries so far (zero before the bin's first chunk).
 template <int JN>
 __device__ __forceinline__ void bds_emit_chunk(BdsLds& L, const uint32_t (&m)[JN], const uint32_t (&g)[JN],
-                                               uint32_t cnt, int NT, uint32_t* __restrict__ out, uint32_t n) {
+                                               uint32_t cnt, int NT, uint32_t* __restrict__ out, uint32_t n,
+                                               uint32_t (&run)[2]) {
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  uint32_t mine = 0;  // lane k < NT: this wave's entries of tile k
-  static_for<0, JN>([&](auto J) {
-    constexpr int j = decltype(J)::value;
-    if ((uint32_t)(w * JN + j) * 64u < cnt) {  // wave-uniform
-      const uint32_t mj = m[j];
-#pragma unroll 1
-      for (int k = 0; k < NT; ++k) {  // (k: an SGPR)
-        const uint64_t b = wave_ballot((mj >> k) & 1u);
-        mine += lane == k ? (uint32_t)__popcll(b) : 0u;
-      }
-    }
-  });
-  if (lane < 16) L.etot[w][lane] = mine;
+#pragma unroll
+  for (int j = 0; j < JN; ++j)
+    if ((uint32_t)(w * JN + j) * 64u < cnt)  // wave-uniform: whole groups, the last one zero-padded
+      L.buf[(uint32_t)(w * JN + j) * 64u + (uint32_t)lane] = make_uint2(m[j], g[j]);
   __syncthreads();
-  uint32_t pre = 0;  // lane k: first slot of this wave's entries of tile k
-  if (lane < NT) {
-    pre = L.erun[lane];
-    for (int q = 0; q < w; ++q) pre += L.etot[q][lane];
-  }
-  static_for<0, JN>([&](auto J) {
-    constexpr int j = decltype(J)::value;
-    if ((uint32_t)(w * JN + j) * 64u < cnt) {
-      const uint32_t mj = m[j], gj = g[j];
-#pragma unroll 1
-      for (int k = 0; k < NT; ++k) {
-        const bool bit = (mj >> k) & 1u;
-        const uint64_t b = wave_ballot(bit);
-        if (b != 0) {  // wave-uniform
-          const uint32_t base = (uint32_t)__builtin_amdgcn_readlane((int)pre, k);
-          if (bit) out[(size_t)k * n + base + lanes_below(b)] = gj;
-          pre += lane == k ? (uint32_t)__popcll(b) : 0u;
-        }
-      }
-    }
-  });
-  __syncthreads();  // every wave has read erun
-  if (w == kBdsWaves - 1 && lane < NT) L.erun[lane] = pre;  // the last wave's end = the running totals
-  __syncthreads();
+  if (NT == 16)
+    bds_emit_walk<2>(L, cnt, out, n, run);
+  else
+    bds_emit_walk<1>(L, cnt, out, n, run);
+  __syncthreads();  // the buffer is restaged by the next chunk; ecnt is read by bds_emit_ranges
 }
 
 // the bin's ranges / list lengths (and the lists' location flag), after its last chunk
@@ -940,7 +981,7 @@ __device__ __forceinline__ void bds_emit_ranges(const BdsLds& L, const BdsEmit& 
     if (tx < E.gx && ty < E.gy) {
       const uint32_t tile = (uint32_t)ty * (uint32_t)E.gx + (uint32_t)tx;
       const uint32_t b0 = (lo << (2 * E.bshift)) + (uint32_t)t * n;
-      const uint32_t c_t = n ? L.erun[t] : 0u;
+      const uint32_t c_t = n ? L.ecnt[t] : 0u;
       E.ranges[tile] = make_uint2(b0, b0 + c_t);
       E.tile_len[tile] = c_t;
     }
@@ -1132,9 +1173,8 @@ __device__ __forceinline__ void bds_small(BdsLds& L, const uint32_t* __restrict_
       m[j] = le < n ? (m[j] >> 16) & tmask : 0u;
       g[j] = le < n ? g[j] : 0u;
     }
-    if (t < 16) L.erun[t] = 0u;
-    __syncthreads();
-    bds_emit_chunk<JN>(L, m, g, n, 1 << (2 * EM.bshift), EM.lists + ((size_t)lo << (2 * EM.bshift)), n);
+    uint32_t run[2] = {0u, 0u};
+    bds_emit_chunk<JN>(L, m, g, n, 1 << (2 * EM.bshift), EM.lists + ((size_t)lo << (2 * EM.bshift)), n, run);
     return;
   }
   // every gather load issued before the first store (unconditional, clamped)
@@ -1164,27 +1204,33 @@ template <int JN>
 __device__ __forceinline__ void bds_emit_big(BdsLds& L, const uint32_t* __restrict__ skeys,
                                              const uint32_t* __restrict__ sgid, const uint2* fin, uint32_t lo,
                                              uint32_t n, const BdsEmit& E) {
-  const int t = threadIdx.x, w = t >> 6, lane = t & 63;
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const uint32_t tmask = (1u << (1 << (2 * E.bshift))) - 1u;
   constexpr uint32_t kChunk = JN * kBdsThreads;
-  if (t < 16) L.erun[t] = 0u;
-  __syncthreads();
   uint32_t* out = E.lists + ((size_t)lo << (2 * E.bshift));
+  uint32_t run[2] = {0u, 0u};
   for (uint32_t c0 = 0; c0 < n; c0 += kChunk) {
     const uint32_t cn = min(kChunk, n - c0);
+    // (loads of clamped positions, every one issued before the first is used)
     uint32_t m[JN], g[JN];
+#pragma unroll
+    for (int j = 0; j < JN; ++j) g[j] = c0 + min((uint32_t)(w * JN + j) * 64u + (uint32_t)lane, cn - 1u);
+    if (fin) {  // (uniform)
+#pragma unroll
+      for (int j = 0; j < JN; ++j) g[j] = bds_load_scratch(fin + g[j]).y;
+    }
+#pragma unroll
+    for (int j = 0; j < JN; ++j) {
+      m[j] = skeys[lo + g[j]];
+      g[j] = sgid[lo + g[j]];
+    }
 #pragma unroll
     for (int j = 0; j < JN; ++j) {
       const uint32_t le = (uint32_t)(w * JN + j) * 64u + (uint32_t)lane;
-      m[j] = 0u;
-      g[j] = 0u;
-      if (le < cn) {
-        const uint32_t q = fin ? bds_load_scratch(fin + c0 + le).y : c0 + le;
-        m[j] = (skeys[lo + q] >> 16) & tmask;
-        g[j] = sgid[lo + q];
-      }
+      m[j] = le < cn ? (m[j] >> 16) & tmask : 0u;
+      g[j] = le < cn ? g[j] : 0u;
     }
-    bds_emit_chunk<JN>(L, m, g, cn, 1 << (2 * E.bshift), out, n);
+    bds_emit_chunk<JN>(L, m, g, cn, 1 << (2 * E.bshift), out, n, run);
   }
 }
 

@@ -118,12 +118,31 @@ def se3_exp(tau: torch.Tensor) -> torch.Tensor:
 
 def rasterize_dense(means3D, means2D, opacities, shs, colors_precomp, scales, rotations,
                     cov3D_precomp, tau, *, H, W, tanfovx, tanfovy, bg, scale_modifier,
-                    viewmatrix, projmatrix, projmatrix_raw, sh_degree, campos, touch_threshold=0.5):
+                    viewmatrix, projmatrix, projmatrix_raw, sh_degree, campos, touch_threshold=0.5,
+                    near_delta=None):
     """Dense forward.  All tensor arguments float64 (leaf tensors may require
     grad).  ``tau`` = [rho(3), theta(3)] (pose delta, zero in every caller).
 
     Returns dict(color[3,H,W], depth[1,H,W], opacity[1,H,W], radii[P] int,
     n_touched[P] int, num_rendered int).
+
+    ``near_delta`` (off by default; nothing else changes when it is on) adds a
+    report of the decisions a float32 implementation may take the other way:
+      near_pixels [H,W] bool  while the pixel still blends (up to and including
+                              the entry of its first T < 1e-4 stop) some list
+                              entry has |255 alpha - 1|, |power| or (valid
+                              entries) |T / 1e-4 - 1| below near_delta;
+      near_rows [P] bool      an SH colour within near_delta of its clamp at 0,
+                              |t.x / t.z| or |t.y / t.z| within a relative
+                              near_delta of the frustum clamp, or the view
+                              depth within a relative near_delta of the 0.2
+                              cull (the last one flagged whether or not this
+                              precision culls the Gaussian);
+    and what the test cases are picked by: stopped [H,W] bool (the pixel hit
+    the T < 1e-4 stop), list_len [gy,gx] (tile list lengths), rect [P,4]
+    (tile rectangle min x, min y, max x, max y; max exclusive), sat_entries
+    (blended entries with o G > 0.99) and sh_clamped [P] bool (a colour channel
+    clamped at 0).
     """
     dt = torch.float64
     P = means3D.shape[0]
@@ -221,6 +240,21 @@ def rasterize_dense(means3D, means2D, opacities, shs, colors_precomp, scales, ro
         dirs = dirs / dirs.norm(dim=1, keepdim=True)
         rgb = torch.clamp_min(eval_sh(sh_degree, shs[:, :K], dirs) + 0.5, 0.0)
     depth = p_view[:, 2]
+    report = None
+    if near_delta is not None:
+        with torch.no_grad():
+            rows = ((txtz.abs() / limx - 1.0).abs() < near_delta) | ((tytz.abs() / limy - 1.0).abs() < near_delta)
+            rows = (rows & visible) | ((depth / NEAR_F32 - 1.0).abs() < near_delta)
+            sh_clamped = torch.zeros(P, dtype=torch.bool)
+            if colors_precomp is None or colors_precomp.numel() == 0:
+                raw = eval_sh(sh_degree, shs[:, :K], dirs) + 0.5
+                rows |= visible & (raw.abs() < near_delta).any(1)
+                sh_clamped = visible & (raw < 0).any(1)
+            report = dict(near_rows=rows, sh_clamped=sh_clamped, sat_entries=0,
+                          rect=torch.stack([rminx, rminy, rmaxx, rmaxy], dim=1),
+                          list_len=torch.zeros(gy, gx, dtype=torch.int64))
+            near_t = [[None] * gx for _ in range(gy)]
+            stop_t = [[None] * gx for _ in range(gy)]
     opac = opacities.reshape(-1)
 
     # ---- per-tile compositing (A.3), depth order stable by index
@@ -247,6 +281,9 @@ def rasterize_dense(means3D, means2D, opacities, shs, colors_precomp, scales, ro
                 out_c[ty_][tx_] = bgd[:, None].expand(3, npx)
                 out_d[ty_][tx_] = torch.zeros(1, npx, dtype=dt)
                 out_t[ty_][tx_] = torch.ones(1, npx, dtype=dt)
+                if report is not None:
+                    near_t[ty_][tx_] = torch.zeros(1, npx, dtype=torch.bool)
+                    stop_t[ty_][tx_] = torch.zeros(1, npx, dtype=torch.bool)
                 continue
             py, px = torch.meshgrid(torch.arange(y0, y1, dtype=dt),
                                     torch.arange(x0, x1, dtype=dt), indexing="ij")
@@ -275,6 +312,15 @@ def rasterize_dense(means3D, means2D, opacities, shs, colors_precomp, scales, ro
             with torch.no_grad():
                 touched = keep & valid & (Tinc > touch_threshold)
                 n_touched.index_add_(0, L, touched.sum(0))
+                if report is not None:
+                    nstop = torch.cumsum(stop.to(torch.int64), dim=1)
+                    blending = (nstop - stop.to(torch.int64)) == 0  # up to and including the stop entry
+                    near = ((255.0 * alpha - 1.0).abs() < near_delta) | (power.abs() < near_delta)
+                    near |= valid & ((Tinc / 1e-4 - 1.0).abs() < near_delta)
+                    near_t[ty_][tx_] = (near & blending).any(1)[None]
+                    stop_t[ty_][tx_] = stop.any(1)[None]
+                    report["list_len"][ty_, tx_] = L.numel()
+                    report["sat_entries"] += int((keep & valid & (araw > 0.99)).sum())
             out_c[ty_][tx_] = (Cc + Tf * bgd[None, :]).T
             out_d[ty_][tx_] = Dd.T
             out_t[ty_][tx_] = Tf.T
@@ -290,7 +336,12 @@ def rasterize_dense(means3D, means2D, opacities, shs, colors_precomp, scales, ro
     color = assemble(out_c, 3)
     depth_img = assemble(out_d, 1)
     T_img = assemble(out_t, 1)
-    return dict(color=color, depth=depth_img, opacity=1.0 - T_img,
+    if report is not None:
+        report["near_pixels"] = assemble(near_t, 1)[0]
+        report["stopped"] = assemble(stop_t, 1)[0]
+    else:
+        report = {}
+    return dict(**report, color=color, depth=depth_img, opacity=1.0 - T_img,
                 radii=radii.to(torch.int32), n_touched=n_touched.to(torch.int32),
                 num_rendered=int(tiles.sum()), tiles_touched=tiles,
                 # per-Gaussian geometry (detached; tests cross-check it against
@@ -299,10 +350,14 @@ def rasterize_dense(means3D, means2D, opacities, shs, colors_precomp, scales, ro
                 rgb=rgb.detach(), visible=visible)
 
 
-def dense_forward_backward(scene: dict, settings: dict, grad_color, grad_depth):
+def dense_forward_backward(scene: dict, settings: dict, grad_color, grad_depth, near_delta=None,
+                           mask_near=False):
     """Run the dense forward, backprop (dL/dcolor, dL/ddepth) and return
     forward outputs + gradients in the layout of
-    ``_C.rasterize_gaussians_backward``."""
+    ``_C.rasterize_gaussians_backward``.
+
+    ``near_delta`` adds rasterize_dense's report; with ``mask_near`` the
+    upstream gradients are zeroed at its near pixels before the backward."""
     dt = torch.float64
 
     def leaf(x):
@@ -321,7 +376,10 @@ def dense_forward_backward(scene: dict, settings: dict, grad_color, grad_depth):
     cov = leaf(scene.get("cov3D_precomp"))
     tau = torch.zeros(6, dtype=dt, requires_grad=True)
     out = rasterize_dense(means3D, means2D, opac, shs, colors, scales, rots, cov, tau,
-                          **settings)
+                          **settings, **({} if near_delta is None else dict(near_delta=near_delta)))
+    if mask_near:
+        far = ~out["near_pixels"]
+        grad_color, grad_depth = grad_color * far, grad_depth * far
     loss = (out["color"] * grad_color.to(dt)).sum() + (out["depth"] * grad_depth.to(dt)).sum()
     if loss.requires_grad:  # nothing visible -> every gradient is zero
         loss.backward()

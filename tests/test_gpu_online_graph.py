@@ -262,6 +262,28 @@ def test_graph_capacity_overflow_recovers():
         assert torch.isfinite(m.ms.store.param(n)).all()
 
 
+def test_capture_suspends_the_cyclic_collector():
+    """A finished mapper is cyclic garbage holding graphs and pinned buffers;
+    the collector must not run (and release them) inside a stream capture."""
+    import gc
+    from types import SimpleNamespace
+    from wgsr.online_graph import IterationGraphs
+    holder = SimpleNamespace(stream=torch.cuda.Stream(DEV), pool=torch.cuda.graph_pool_handle())
+    x = torch.zeros(8, device=DEV)
+    holder.stream.wait_stream(torch.cuda.current_stream(DEV))
+    seen = []
+
+    def body():
+        seen.append(gc.isenabled())
+        x.add_(1.0)
+    assert gc.isenabled()
+    g = IterationGraphs._capture_one(holder, body)
+    assert seen == [False] and gc.isenabled()
+    g.replay()
+    torch.cuda.synchronize()
+    assert x.tolist() == [1.0] * 8
+
+
 def test_random_perm_gather_exposure_step_and_mlp_accumulate():
     from wgsr import _lib
     from wgsr.mlp import UncertaintyMLP, _mix32, backward_raw, forward_raw

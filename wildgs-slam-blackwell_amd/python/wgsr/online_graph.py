@@ -42,6 +42,7 @@ they are recaptured lazily.
 """
 from __future__ import annotations
 
+import gc
 import math
 import os
 import time
@@ -429,12 +430,23 @@ class IterationGraphs:
         """One graph of ``fn``'s device work on the capture stream, in the
         shared pool."""
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.stream(self.stream):
-            g.capture_begin(pool=self.pool)
-            try:
-                fn()
-            finally:
-                g.capture_end()
+        # No cyclic collection while the stream captures: a finished mapper is
+        # cyclic garbage (mapper <-> IterationGraphs) that owns graphs, pinned
+        # buffers and pool memory, and the collector releasing those in the
+        # middle of a capture aborts the process.  (Suspended, not run first:
+        # a gc.collect() per capture costs tens of ms.)
+        gc_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.stream(self.stream):
+                g.capture_begin(pool=self.pool)
+                try:
+                    fn()
+                finally:
+                    g.capture_end()
+        finally:
+            if gc_on:
+                gc.enable()
         return g
 
     def _capture_body(self, nbc: int, refine: bool):

@@ -259,6 +259,13 @@ size_t bin_depth_max_avg() {
   const char* e = getenv("WGSR_BIN_DEPTH_MAX_AVG");  // (per call: tests force the fallback)
   return e ? (size_t)strtoull(e, nullptr, 10) : (size_t)6144;
 }
+// Threads on each tile of the bin sort's wide pass (WGSR_BIN_SORT_THREADS =
+// 256, 512 or 1024; unset or anything else: kWideSortThreads on 4096-key
+// tiles, 256 on the smaller sorts' tiles).
+int bin_sort_threads() {
+  const char* e = getenv("WGSR_BIN_SORT_THREADS");  // (per call: tests compare the variants)
+  return e ? atoi(e) : 0;
+}
 constexpr int kDepthBits = 32;
 constexpr bool kFullDepthInAlt = ((kDepthBits + 7) / 8) % 2 == 1;
 // byte offset of the last forward's depth order (rank -> Gaussian) in its
@@ -580,7 +587,8 @@ int queue_lists_and_render(const Fwd& f, void* binning, const BinningPlan& plan,
     { StageTimer T(kStTileSort, s);
     STAGE(a, s, radix_sort_pairs(at<uint32_t>(binning, BL.key), at<uint32_t>(binning, BL.key_alt), vin, valt, false,
                                  NL, 0, bits, at<uint32_t>(binning, BL.hist), at<uint32_t>(binning, BL.totals), s,
-                                 &talt, bin_bounds, &bounds_done, bs_words != 0, ndev)); }
+                                 &talt, bin_bounds, &bounds_done, bs_words != 0, ndev,
+                                 bshift ? bin_sort_threads() : 0)); }
     // the Gaussian ids are the payload; the backward recomputes each pair's
     // record slot from (Gaussian, tile) instead of carrying it through the sort
     if (talt != odd) return set_error(WGSR_EHIP, "internal: list sort parity");

@@ -42,6 +42,20 @@ __device__ __forceinline__ uint32_t block_excl_scan256(uint32_t v, uint32_t* s_t
   return base + inc - v;
 }
 
+// the same over a workgroup of NW waves
+template <int NW>
+__device__ __forceinline__ uint32_t block_excl_scan_waves(uint32_t v, uint32_t* s_tmp) {
+  const int t = threadIdx.x, w = t >> 6, lane = t & 63;
+  uint32_t inc = wave_incl_scan(v);
+  if (lane == 63) s_tmp[w] = inc;
+  __syncthreads();
+  uint32_t base = 0;
+#pragma unroll
+  for (int i = 0; i < NW; ++i) base += (i < w) ? s_tmp[i] : 0u;
+  __syncthreads();
+  return base + inc - v;
+}
+
 // ---- digit counting ----------------------------------------------------------
 // Histogram kernels give thread t of a block the I CONTIGUOUS keys
 // [I t, I t + I) of the block's 256 I and count them one LDS atomic per run
@@ -51,8 +65,7 @@ __device__ __forceinline__ uint32_t block_excl_scan256(uint32_t v, uint32_t* s_t
 
 template <int I>
 __device__ __forceinline__ int load_run(const uint32_t* __restrict__ keys, size_t n, size_t e0, uint32_t (&k)[I]) {
-  static_assert(I % 4 == 0, "load_run reads uint4s");
-  if (e0 + I <= n) {
+  if (I % 4 == 0 && e0 + I <= n) {  // (runs of 4 k keys as uint4s)
     const uint4* p = reinterpret_cast<const uint4*>(keys + e0);
 #pragma unroll
     for (int q = 0; q < I / 4; ++q) {
@@ -273,51 +286,85 @@ __global__ __launch_bounds__(256) void k_radix_scatter(
 // ---- wide single pass (9-10 bit digits) ------------------------------------
 // A sort on 9 or 10 bits (the 510 sort bins of a 1080p frame) in ONE
 // stable pass instead of two 8-bit-or-less passes: the same reduce-then-scan
-// structure with DIG digits, each thread owning DIG / 256 consecutive digits
-// in the per-digit steps.
-template <int DIG, int I>
-__global__ __launch_bounds__(256) void k_radix_hist_wide(const uint32_t* __restrict__ keys, uint32_t n, int shift,
-                                                         int bits, uint32_t nb, uint32_t* __restrict__ hist,
-                                                         const uint32_t* __restrict__ ndev) {
+// structure with DIG digits.  A workgroup of NT threads (256, 512 or 1024)
+// owns the same 256 I keys whatever NT is, K = 256 I / NT per thread; in the
+// per-digit steps thread t owns the DIG / NT consecutive digits from
+// t DIG / NT (one digit, and none beyond DIG, when NT >= DIG).
+template <int DIG, int NT, int I>
+__global__ __launch_bounds__(NT) void k_radix_hist_wide(const uint32_t* __restrict__ keys, uint32_t n, int shift,
+                                                        int bits, uint32_t nb, uint32_t* __restrict__ hist,
+                                                        const uint32_t* __restrict__ ndev) {
+  constexpr int kT = 256 * I, K = kT / NT;
+  static_assert(K >= 1 && K * NT == kT, "whole keys per thread");
   __shared__ uint32_t s_h[DIG];
   const int t = threadIdx.x;
   if (ndev) n = min(n, *ndev);
-#pragma unroll
-  for (int k = 0; k < DIG / 256; ++k) s_h[t + 256 * k] = 0;
-  uint32_t key[I];
-  const int nv = load_run<I>(keys, n, (size_t)blockIdx.x * (256 * I) + (size_t)t * I, key);
+  for (int d = t; d < DIG; d += NT) s_h[d] = 0;
+  uint32_t key[K];
+  const int nv = load_run<K>(keys, n, (size_t)blockIdx.x * kT + (size_t)t * K, key);
   __syncthreads();
   add_runs(s_h, key, nv, shift, (1u << bits) - 1u);
   __syncthreads();
-#pragma unroll
-  for (int k = 0; k < DIG / 256; ++k) hist[(size_t)(t + 256 * k) * nb + blockIdx.x] = s_h[t + 256 * k];
+  for (int d = t; d < DIG; d += NT) hist[(size_t)d * nb + blockIdx.x] = s_h[d];
 }
 
-template <int DIG, int I>
-__global__ __launch_bounds__(256) void k_radix_scatter_wide(
+// The scatter's time is one wave's chain of K dependent ranking rounds (nine
+// ballots, an LDS atomic and a shuffle each) plus three barriers, so the same
+// 4096-key tile ranks faster on more waves: K = 16, 8 or 4 rounds at NT = 256,
+// 512 or 1024.  The tile itself stays (2048-key tiles lost, 39.7 vs 35.7 us:
+// the per-digit output runs shrink).  Stable whatever NT is: element order in
+// the tile is wave-major (wave w owns keys [64 K w, 64 K (w + 1))) and the
+// per-wave digit counts s_wcnt[NW][DIG] are prefixed in wave order.
+// Measured at 1M / 1080p (587 tiles, 510 digits): 256
+// threads with ballots 27.6 us (114 VGPRs, 45 KB LDS); 512 threads with
+// ballots 23.7 us; 512 threads with the peer groups from the LDS lane-mask
+// table (below) 21.4 us, the default (63 VGPRs, 53 KB LDS, three workgroups
+// per CU, no scratch).
+// Tried and removed: the pass also writing dout[dst] = gdep[value], the depth
+// key of every sorted (Gaussian, bin) pair, for k_bin_depth_sort to read in
+// order instead of gathering through the ids.  The gather cost the scatter
+// 9.6 us (23.3 -> 32.9, ballots) and saved the depth sort 7.2 (50.1 -> 42.9):
+// 2.4 M uncoalesced 4-byte loads are bound by address throughput, not by
+// latency that the ranking could hide.
+template <int DIG, int NT, int I>
+__global__ __launch_bounds__(NT) void k_radix_scatter_wide(
     const uint32_t* __restrict__ kin, const uint32_t* __restrict__ vin, int iota, uint32_t n, int shift, int bits,
     uint32_t nb, const uint32_t* __restrict__ hist, const uint32_t* __restrict__ totals, uint32_t* __restrict__ kout,
     uint32_t* __restrict__ vout, uint2* __restrict__ digit_bounds, const uint32_t* __restrict__ ndev) {
-  constexpr int kT = 256 * I, DPT = DIG / 256;
+  constexpr int kT = 256 * I, K = kT / NT, NW = NT / 64, DPT = DIG >= NT ? DIG / NT : 1;
+  static_assert(K >= 1 && K * NT == kT && NW * 64 == NT, "whole keys per thread, whole waves");
   if (ndev) {
     n = min(n, *ndev);
     if ((size_t)blockIdx.x * kT >= n && !(blockIdx.x == 0 && digit_bounds)) return;
   }
   __shared__ uint2 s_buf[kT];  // (key, value) in digit order
-  __shared__ uint32_t s_wcnt[4][DIG];
+  __shared__ uint32_t s_wcnt[NW][DIG];
   __shared__ uint32_t s_lbase[DIG];
   __shared__ uint32_t s_gbase[DIG];
-  __shared__ uint32_t s_tmp[4];
+  __shared__ uint32_t s_tmp[NW];
   const int t = threadIdx.x, w = t >> 6, lane = t & 63;
   const uint32_t mask = (1u << bits) - 1u;
-#pragma unroll
-  for (int i = 0; i < 4 * DPT; ++i) (&s_wcnt[0][0])[t + 256 * i] = 0;
+  const bool own = t * DPT < DIG;  // (threads beyond DIG own no digit)
+  for (int i = t; i < NW * DIG; i += NT) (&s_wcnt[0][0])[i] = 0;
+  // Peer groups (the lanes of a wave that share a digit) from a lane-mask
+  // table in LDS, as in k_bin_depth_sort's bds_rank: every lane ORs its bit
+  // into its wave's word for its digit, reads the word back and clears it --
+  // three LDS operations in place of one ballot and a 64-bit select per digit
+  // bit.  A wave's LDS instructions complete in order, so every lane's OR
+  // lands before any lane's read and every read before the clear behind it.
+  // The table takes the staging buffer's place (free until the ranking is
+  // done) and is all zero again when the ranking ends.  Only where NW x DIG
+  // words fit the buffer, and only on the 4096-key tiles it was measured on.
+  constexpr bool kTable = I == kSortItems && NW * DIG <= kT;
+  unsigned long long* s_match = reinterpret_cast<unsigned long long*>(s_buf);  // [NW][DIG]
+  if (kTable)
+    for (int i = t; i < NW * DIG; i += NT) s_match[i] = 0ull;
   const uint32_t bid = blockIdx.x;
   const size_t blk0 = (size_t)bid * kT;
-  const size_t base = blk0 + (size_t)w * (64 * I);
-  uint32_t key[I], val[I], rank[I];
+  const size_t base = blk0 + (size_t)w * (64 * K);
+  uint32_t key[K], val[K], rank[K];
 #pragma unroll
-  for (int j = 0; j < I; ++j) {
+  for (int j = 0; j < K; ++j) {
     const size_t e = base + (size_t)j * 64 + lane;
     const bool valid = e < n;
     key[j] = valid ? kin[e] : 0u;
@@ -326,24 +373,34 @@ __global__ __launch_bounds__(256) void k_radix_scatter_wide(
   {  // global base of this block's digits: digit start (scan of totals) + block offset
     uint32_t tot[DPT], s = 0;
 #pragma unroll
-    for (int k = 0; k < DPT; ++k) { tot[k] = totals[t * DPT + k]; s += tot[k]; }
-    uint32_t run = block_excl_scan256(s, s_tmp, nullptr);  // (its barriers publish s_wcnt = 0)
+    for (int k = 0; k < DPT; ++k) { tot[k] = own ? totals[t * DPT + k] : 0u; s += tot[k]; }
+    uint32_t run = block_excl_scan_waves<NW>(s, s_tmp);  // (its barriers publish s_wcnt = 0 and the zeroed table)
 #pragma unroll
     for (int k = 0; k < DPT; ++k) {
       const int d = t * DPT + k;
-      s_gbase[d] = run + hist[(size_t)d * nb + bid];
-      // the sorted output's [start, end) of every digit (the key is the
-      // whole digit: e.g. the bin ranges k_expand_bins needs)
-      if (digit_bounds && bid == 0) digit_bounds[d] = make_uint2(run, run + tot[k]);
+      if (own) {
+        s_gbase[d] = run + hist[(size_t)d * nb + bid];
+        // the sorted output's [start, end) of every digit (the key is the
+        // whole digit: e.g. the bin ranges k_bin_depth_sort needs)
+        if (digit_bounds && bid == 0) digit_bounds[d] = make_uint2(run, run + tot[k]);
+      }
       run += tot[k];
     }
   }
 #pragma unroll
-  for (int j = 0; j < I; ++j) {
+  for (int j = 0; j < K; ++j) {
     const size_t e = base + (size_t)j * 64 + lane;
     const bool valid = e < n;
     const uint32_t d = (key[j] >> shift) & mask;
-    const uint64_t peers = match_digit(d, bits, wave_ballot(valid));
+    uint64_t peers;
+    if (kTable) {
+      unsigned long long* m = &s_match[w * DIG + d];
+      if (valid) atomicOr(m, 1ull << lane);
+      peers = valid ? *m : 0ull;
+      if (valid) *m = 0ull;
+    } else {
+      peers = match_digit(d, bits, wave_ballot(valid));
+    }
     const int leader = __ffsll((unsigned long long)peers) - 1;
     uint32_t old = 0;
     if (valid && lane == leader) old = atomicAdd(&s_wcnt[w][d], (uint32_t)__popcll(peers));
@@ -351,39 +408,43 @@ __global__ __launch_bounds__(256) void k_radix_scatter_wide(
     rank[j] = old + lanes_below(peers);
   }
   __syncthreads();
-  {  // per digit: exclusive prefix over waves, then over digits (block-local)
+  {  // per digit: exclusive prefix over waves (in wave order), then over digits (block-local)
     uint32_t cnt[DPT], s = 0;
 #pragma unroll
     for (int k = 0; k < DPT; ++k) {
       const int d = t * DPT + k;
-      const uint32_t c0 = s_wcnt[0][d], c1 = s_wcnt[1][d], c2 = s_wcnt[2][d], c3 = s_wcnt[3][d];
-      cnt[k] = c0 + c1 + c2 + c3;
-      s += cnt[k];
-      s_wcnt[0][d] = 0;
-      s_wcnt[1][d] = c0;
-      s_wcnt[2][d] = c0 + c1;
-      s_wcnt[3][d] = c0 + c1 + c2;
+      uint32_t run = 0;
+      if (own) {
+#pragma unroll
+        for (int q = 0; q < NW; ++q) {
+          const uint32_t c = s_wcnt[q][d];
+          s_wcnt[q][d] = run;
+          run += c;
+        }
+      }
+      cnt[k] = run;
+      s += run;
     }
-    uint32_t run = block_excl_scan256(s, s_tmp, nullptr);
+    uint32_t run = block_excl_scan_waves<NW>(s, s_tmp);
 #pragma unroll
     for (int k = 0; k < DPT; ++k) {
-      s_lbase[t * DPT + k] = run;
+      if (own) s_lbase[t * DPT + k] = run;
       run += cnt[k];
     }
   }
   __syncthreads();
 #pragma unroll
-  for (int j = 0; j < I; ++j) {
+  for (int j = 0; j < K; ++j) {
     const size_t e = base + (size_t)j * 64 + lane;
     const uint32_t d = (key[j] >> shift) & mask;
-    const uint32_t slot = s_lbase[d] + s_wcnt[w][d] + rank[j];
+    const uint32_t slot = s_lbase[d] + s_wcnt[w][d] + rank[j];  // in the tile's digit order
     if (e < n) s_buf[slot] = make_uint2(key[j], val[j]);
   }
   __syncthreads();
   const uint32_t cnt = (size_t)n > blk0 ? (uint32_t)min((size_t)kT, (size_t)n - blk0) : 0u;
 #pragma unroll
-  for (int r = 0; r < I; ++r) {
-    const uint32_t i = (uint32_t)t + 256u * r;
+  for (int r = 0; r < K; ++r) {
+    const uint32_t i = (uint32_t)t + (uint32_t)NT * r;
     if (i < cnt) {
       const uint2 kv = s_buf[i];
       const uint32_t d = (kv.x >> shift) & mask;
@@ -800,31 +861,42 @@ size_t sort_sup_words(size_t n, int begin_bit, int end_bit, size_t* offset_words
   return 256 * (size_t)((nb + kSupBlocks - 1) / kSupBlocks) * ((bits + 7) / 8);
 }
 
+// the wide pass with NT threads on each tile of 256 I keys
+template <int DIG, int NT, int I>
+static void launch_wide_pass(uint32_t* keys, uint32_t* keys_alt, uint32_t* vals, uint32_t* vals_alt, bool vals_iota,
+                             uint32_t n, int begin_bit, int bits, uint32_t nb, uint32_t* status, uint32_t* totals,
+                             hipStream_t stream, uint2* digit_bounds, const uint32_t* ndev) {
+  // status doubles as the [DIG][nb] per-block histogram (DIG <= 1024 <= 256 x kMaxSortPasses rows)
+  hipLaunchKernelGGL((k_radix_hist_wide<DIG, NT, I>), dim3(nb), dim3(NT), 0, stream, keys, n, begin_bit, bits, nb,
+                     status, ndev);
+  hipLaunchKernelGGL(k_radix_rowscan, dim3(DIG), dim3(256), 0, stream, status, nb, totals);
+  hipLaunchKernelGGL((k_radix_scatter_wide<DIG, NT, I>), dim3(nb), dim3(NT), 0, stream, keys, vals, vals_iota ? 1 : 0,
+                     n, begin_bit, bits, nb, status, totals, keys_alt, vals_alt, digit_bounds, ndev);
+}
+
 // one sort with I keys per thread (workgroup tile 256 I)
 template <int I>
 static hipError_t radix_sort_tiled(uint32_t* keys, uint32_t* keys_alt, uint32_t* vals, uint32_t* vals_alt,
                                    bool vals_iota, size_t n, int begin_bit, int end_bit, uint32_t* status,
                                    uint32_t* totals, hipStream_t stream, bool* result_in_alt, uint2* digit_bounds,
-                                   bool* bounds_done, bool sup_zeroed, const uint32_t* ndev) {
+                                   bool* bounds_done, bool sup_zeroed, const uint32_t* ndev, int wide_threads) {
   const uint32_t nb = sort_blocks(n);
   if (wide_pass(end_bit - begin_bit) && n <= (size_t)kStCount) {
     const int bits = end_bit - begin_bit;
-    // status doubles as the [DIG][nb] per-block histogram (DIG <= 1024 <= 256 x kMaxSortPasses rows)
+    // threads per tile: the caller's choice, else kWideSortThreads on the
+    // 4096-key tiles it was measured on (smaller sorts as before)
+    int nt = wide_threads;
+    if (nt != 256 && nt != 512 && nt != 1024) nt = I == kSortItems ? kWideSortThreads : 256;
+    uint2* db = begin_bit == 0 ? digit_bounds : nullptr;
+#define WGSR_WIDE(DIG, NT)                                                                                         \
+  launch_wide_pass<DIG, NT, I>(keys, keys_alt, vals, vals_alt, vals_iota, (uint32_t)n, begin_bit, bits, nb, status, \
+                               totals, stream, db, ndev)
     if (bits <= 9) {
-      hipLaunchKernelGGL((k_radix_hist_wide<512, I>), dim3(nb), dim3(256), 0, stream, keys, (uint32_t)n, begin_bit,
-                         bits, nb, status, ndev);
-      hipLaunchKernelGGL(k_radix_rowscan, dim3(512), dim3(256), 0, stream, status, nb, totals);
-      hipLaunchKernelGGL((k_radix_scatter_wide<512, I>), dim3(nb), dim3(256), 0, stream, keys, vals,
-                         vals_iota ? 1 : 0, (uint32_t)n, begin_bit, bits, nb, status, totals, keys_alt, vals_alt,
-                         begin_bit == 0 ? digit_bounds : nullptr, ndev);
+      if (nt == 256) WGSR_WIDE(512, 256); else if (nt == 512) WGSR_WIDE(512, 512); else WGSR_WIDE(512, 1024);
     } else {
-      hipLaunchKernelGGL((k_radix_hist_wide<1024, I>), dim3(nb), dim3(256), 0, stream, keys, (uint32_t)n, begin_bit,
-                         bits, nb, status, ndev);
-      hipLaunchKernelGGL(k_radix_rowscan, dim3(1024), dim3(256), 0, stream, status, nb, totals);
-      hipLaunchKernelGGL((k_radix_scatter_wide<1024, I>), dim3(nb), dim3(256), 0, stream, keys, vals,
-                         vals_iota ? 1 : 0, (uint32_t)n, begin_bit, bits, nb, status, totals, keys_alt, vals_alt,
-                         begin_bit == 0 ? digit_bounds : nullptr, ndev);
+      if (nt == 256) WGSR_WIDE(1024, 256); else if (nt == 512) WGSR_WIDE(1024, 512); else WGSR_WIDE(1024, 1024);
     }
+#undef WGSR_WIDE
     *result_in_alt = true;
     if (bounds_done) *bounds_done = digit_bounds && begin_bit == 0;
     return hipGetLastError();
@@ -869,7 +941,7 @@ static hipError_t radix_sort_tiled(uint32_t* keys, uint32_t* keys_alt, uint32_t*
 hipError_t radix_sort_pairs(uint32_t* keys, uint32_t* keys_alt, uint32_t* vals, uint32_t* vals_alt, bool vals_iota,
                             size_t n, int begin_bit, int end_bit, uint32_t* status, uint32_t* totals,
                             hipStream_t stream, bool* result_in_alt, uint2* digit_bounds, bool* bounds_done,
-                            bool sup_zeroed, const uint32_t* ndev) {
+                            bool sup_zeroed, const uint32_t* ndev, int wide_threads) {
   *result_in_alt = false;
   if (bounds_done) *bounds_done = false;
   if (n == 0 || end_bit <= begin_bit) {
@@ -883,15 +955,15 @@ hipError_t radix_sort_pairs(uint32_t* keys, uint32_t* keys_alt, uint32_t* vals, 
     case kTinySortItems:
       return radix_sort_tiled<kTinySortItems>(keys, keys_alt, vals, vals_alt, vals_iota, n, begin_bit, end_bit, status,
                                               totals, stream, result_in_alt, digit_bounds, bounds_done, sup_zeroed,
-                                              ndev);
+                                              ndev, wide_threads);
     case kSmallSortItems:
       return radix_sort_tiled<kSmallSortItems>(keys, keys_alt, vals, vals_alt, vals_iota, n, begin_bit, end_bit,
                                                status, totals, stream, result_in_alt, digit_bounds, bounds_done,
-                                               sup_zeroed, ndev);
+                                               sup_zeroed, ndev, wide_threads);
     default:
       return radix_sort_tiled<kSortItems>(keys, keys_alt, vals, vals_alt, vals_iota, n, begin_bit, end_bit, status,
                                           totals, stream, result_in_alt, digit_bounds, bounds_done, sup_zeroed,
-                                          ndev);
+                                          ndev, wide_threads);
   }
 }
 

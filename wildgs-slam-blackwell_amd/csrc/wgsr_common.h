@@ -746,7 +746,17 @@ __host__ __device__ constexpr size_t align256(size_t x) { return (x + 255) & ~si
 #ifndef WGSR_TINY_SORT_ITEMS
 #define WGSR_TINY_SORT_ITEMS 4
 #endif
+// (the tile is 256 x kSortItems keys whatever the workgroup size: 2048-key
+// tiles lost for the 2.4 M bin pairs, scatter 39.7 vs 35.7 us, round 5)
 constexpr int kSortItems = 16;
+// threads on each 4096-key tile of the wide (9-10 bit) pass: the bin sort of
+// a 1080p frame (k_radix_scatter_wide, sort.hip; WGSR_BIN_SORT_THREADS).
+// 1M / 1080p, scatter alone: 256 threads 27.6 us, 512 threads 23.7 us (21.4
+// with the LDS peer table); with the since-removed depth-key write in the
+// kernel 256 / 512 / 1024 threads gave 40.0 / 32.9 / 35.6 us (1024: two
+// workgroups per CU, 512 slots for the 587 tiles).  Sorts with smaller tiles
+// keep 256 threads (not measured).
+constexpr int kWideSortThreads = 512;
 constexpr int kSmallSortItems = WGSR_SMALL_SORT_ITEMS;
 constexpr int kTinySortItems = WGSR_TINY_SORT_ITEMS;
 constexpr size_t kSmallSortN = size_t(1) << 21;

@@ -17,11 +17,13 @@ namespace wgsr {
 // one wide pass over bits [0, end_bit), each digit's [start, end) in the
 // sorted output is written there (*bounds_done = true).
 int radix_passes(int begin_bit, int end_bit);
+// wide_threads: threads on each tile of a wide (9-10 bit) pass -- 256, 512 or
+// 1024; anything else: the default (kWideSortThreads on 4096-key tiles).
 hipError_t radix_sort_pairs(uint32_t* keys, uint32_t* keys_alt, uint32_t* vals, uint32_t* vals_alt, bool vals_iota,
                             size_t n, int begin_bit, int end_bit, uint32_t* status, uint32_t* totals,
                             hipStream_t stream, bool* result_in_alt,
                             uint2* digit_bounds = nullptr, bool* bounds_done = nullptr, bool sup_zeroed = false,
-                            const uint32_t* ndev = nullptr);
+                            const uint32_t* ndev = nullptr, int wide_threads = 0);
 // (ndev: capacity mode -- n is the capacity the grid is sized for, *ndev the
 // live key count, read on the device; reduce-then-scan / wide schedules only)
 // words of `status` a reduce-then-scan sort accumulates superblock sums in

@@ -290,16 +290,21 @@ def test_random_perm_gather_exposure_step_and_mlp_accumulate():
     L = _lib.load()
     st = _lib.stream_handle(DEV)
     p = _lib.ptr
-    # wgsr_random_perm == numpy's stable argsort of the restated keys
-    seed, n = 987654321, 4860
-    keys = torch.empty(n, dtype=torch.int32, device=DEV)
-    perm = torch.empty(n, dtype=torch.int32, device=DEV)
-    _lib.check(L.wgsr_random_perm(n, seed, None, p(keys), p(perm), st))
-    with np.errstate(over="ignore"):
-        i = np.arange(n, dtype=np.uint32)
-        want = (_mix32(np.uint32(seed) ^ _mix32(i * np.uint32(0x9E3779B9) + np.uint32(0x632BE5AB))) >> 1)
-    assert np.array_equal(perm.cpu().numpy(), np.argsort(want.astype(np.int64), kind="stable"))
-    assert int(L.wgsr_random_perm_max()) >= 4096
+    # wgsr_random_perm == numpy's stable argsort of the restated keys, at the
+    # edges of the one-workgroup sort's entry groups (64) and of its three
+    # entries-per-lane choices (1024, 2048, the maximum); nothing written past n
+    seed, nmax = 987654321, int(L.wgsr_random_perm_max())
+    assert nmax >= 4096
+    for n in (0, 1, 63, 64, 65, 1024, 1025, 2048, 2049, 4860, nmax):
+        keys = torch.full((nmax + 64,), -7, dtype=torch.int32, device=DEV)
+        perm = torch.full((nmax + 64,), -7, dtype=torch.int32, device=DEV)
+        _lib.check(L.wgsr_random_perm(n, seed, None, p(keys), p(perm), st))
+        with np.errstate(over="ignore"):
+            i = np.arange(n, dtype=np.uint32)
+            want = (_mix32(np.uint32(seed) ^ _mix32(i * np.uint32(0x9E3779B9) + np.uint32(0x632BE5AB))) >> 1)
+        got = perm.cpu().numpy()
+        assert np.array_equal(got[:n], np.argsort(want.astype(np.int64), kind="stable")), n
+        assert (got[n:] == -7).all() and (keys.cpu().numpy()[n:] == -7).all(), n
     # wgsr_gather_rows: rows by a device index, vector and scalar jobs, a strided source
     g = torch.Generator(device=DEV).manual_seed(0)
     bank = torch.randn(10, 3, 8, 12, device=DEV, generator=g)

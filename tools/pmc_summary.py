@@ -36,7 +36,7 @@ STAGE_OF = {
     "k_render_fwd_quad": "render_fwd", "k_render_bwd_quad": "render_bwd", "k_sum_partials": "gauss_bwd",
     "k_render_fwd1": "render_fwd", "k_tile_order": "render_bwd",
     "k_scan_reduce": "offsets_scan", "k_scan_bsum": "offsets_scan", "k_scan_down": "offsets_scan",
-    "k_scan2_reduce": "offsets_scan", "k_scan2_bsum": "offsets_scan",
+    "k_scan2_reduce": "offsets_scan",
     "k_duplicate_bins": "duplicate", "k_bin_bounds": "ranges", "k_expand_bins": "ranges",
     "k_render_bwd_split": "render_bwd", "k_sum_active": "gauss_bwd", "k_gauss_bwd_compact": "gauss_bwd",
     "k_depth_hist": "depth_sort", "k_depth_scatter": "depth_sort",

@@ -108,16 +108,6 @@ struct DevCounters {
   int parity = 0;
   bool failed = false;
 };
-// The per-bin depth sort emits the per-tile lists itself at every bin shift
-// (bds_emit_walk, raster_fwd.hip: each wave walks the sorted bin once for the
-// tiles it owns).  4 x 4-tile bins, 1M / 1080p: k_bin_depth_sort 39.5 -> 50.1
-// us with k_expand_bins' 29.5 us and its launch gone, 0.7473 -> 0.7325 ms per
-// step; 2 x 2-tile bins (100k 512 x 384, the online loop): 0.1672 -> 0.1665
-// and 0.7223 -> 0.7199 ms.  The earlier lane <-> entry emit
-// (a count pass, a prefix over the waves, a write pass) lost to k_expand_bins
-// at 4 x 4 tiles (140.8 vs 131.3 us) and is gone.
-bool bds_emit(int bshift) { return bshift >= 1 && bshift <= kMaxBinShift; }
-
 DevCounters* dev_counters(hipStream_t s) {
   thread_local DevCounters per_dev[kMaxDevices];
   const int dev = device_slot();
@@ -337,7 +327,7 @@ struct Fwd {
 // agree on it; with sort bins the per-tile lists follow it (2^2s entries per
 // bin pair); then, for the per-bin depth sort, the scratch of the bins beyond
 // one LDS tile (two uint2 ping-pong arrays; not the list region, which the
-// same kernel now writes).
+// same kernel writes).
 struct BinningPlan {
   BinLayout BL;
   size_t lists_bytes, bds_bytes, total;
@@ -538,9 +528,9 @@ int queue_depth_fixup(const Fwd& f, HostCounters& hc, const Counts& c, const uin
 }
 
 // ---- tile lists + render: the tail of both forwards ----
-// duplicate -> bin / tile sort -> per-bin depth sort -> expand or ranges ->
-// render, over NL sorted pairs: (Gaussian, bin) pairs, or with bin shift 0
-// the exact (Gaussian, tile) pairs themselves.  depth_order: rank -> Gaussian
+// duplicate -> bin / tile sort -> per-bin depth sort (which writes the lists),
+// else expand or ranges -> render, over NL sorted pairs: (Gaussian, bin)
+// pairs, or with bin shift 0 the exact (Gaussian, tile) pairs themselves.  depth_order: rank -> Gaussian
 // (null: index order); bin_depth: each bin is ordered by depth after the bin
 // sort.  ndev (capacity mode): NL is the capacity the buffers and grids are
 // sized for and *ndev the live pair count, read on the device.
@@ -554,7 +544,7 @@ int queue_lists_and_render(const Fwd& f, void* binning, const BinningPlan& plan,
   uint2 *ranges = f.im<uint2>(f.IL.ranges), *tile_m = f.im<uint2>(f.IL.tile_m);
   uint32_t *tile_len = f.im<uint32_t>(f.IL.tile_len), *meta = f.im<uint32_t>(f.IL.meta);
   const uint32_t *sorted_keys = nullptr, *sorted_gid = nullptr;
-  bool emit = false, bounds_done = false;
+  bool lists_done = false, bounds_done = false;
   if (NL > 0) {
     const int bits = sort_bits(bshift ? Bins(f.grid.gx, f.grid.gy, bshift).n : f.grid.nt);
     // the LSD sort alternates buffers every pass: start the payload in the
@@ -575,7 +565,7 @@ int queue_lists_and_render(const Fwd& f, void* binning, const BinningPlan& plan,
       // (capacity mode: pairs past the capacity are not written; exact-slot flags likewise)
       const uint32_t cap = ndev ? (uint32_t)NL : 0xFFFFFFFFu;
       STAGE(a, s, launch_duplicate_bins(a, f.geom, depth_order, bshift, at<uint8_t>(binning, BL.flag),
-                                        at<uint32_t>(binning, BL.key), vin, true, zb, meta, s, cap, cap));
+                                        at<uint32_t>(binning, BL.key), vin, zb, meta, s, cap, cap));
     } else {
       STAGE(a, s, launch_duplicate(a, f.geom, depth_order, (uint32_t)a.P, at<uint32_t>(binning, BL.key), vin,
                                    at<uint8_t>(binning, BL.flag), s));
@@ -597,29 +587,21 @@ int queue_lists_and_render(const Fwd& f, void* binning, const BinningPlan& plan,
     if (ndev && !bounds_done) return set_error(WGSR_EHIP, "internal: capacity mode without the sort's bin bounds");
     sorted_keys = at<uint32_t>(binning, talt ? BL.key_alt : BL.key);
     sorted_gid = at<uint32_t>(binning, BL.point_g);
-    emit = bin_depth && bds_emit(bshift);
     if (bin_depth) {
-      // each bin by depth; scratch for bins beyond one LDS tile: the region
-      // behind the lists (>= 16 NL bytes).  With bds_emit it writes the
-      // per-tile lists and ranges itself (no k_expand_bins); else the sorted
-      // bins go to the spare key / payload buffers
+      // each bin by depth (it gathers its keys from the Gaussians' depth
+      // keys), then the per-tile lists and ranges straight from the sorted
+      // bin; scratch for bins beyond one LDS tile: the region behind the
+      // lists (>= 16 NL bytes)
       StageTimer T(kStTileSort, s);
-      uint32_t* okeys = at<uint32_t>(binning, talt ? BL.key : BL.key_alt);
-      uint32_t* ogid = at<uint32_t>(binning, BL.slot_g);
-      // (it gathers its keys from the Gaussians' depth keys)
       STAGE(a, s, launch_bin_depth_sort(a, sorted_keys, sorted_gid, (uint32_t)NL, bshift, tile_m, bounds_done,
-                                        at<uint32_t>(f.geom, f.GL.dkey), okeys, ogid,
-                                        at<char>(binning, BL.total + plan.lists_bytes), s, emit ? lists : nullptr,
-                                        ranges, tile_len, meta));
-      bounds_done = true;
-      if (!emit) {
-        sorted_keys = okeys;
-        sorted_gid = ogid;
-      }
+                                        at<uint32_t>(f.geom, f.GL.dkey),
+                                        at<char>(binning, BL.total + plan.lists_bytes), lists, ranges, tile_len,
+                                        meta, s));
+      lists_done = true;
     }
   }
   { StageTimer T(kStRanges, s);
-  if (emit) {
+  if (lists_done) {
     // (lists and ranges written by the per-bin depth sort)
   } else if (bshift && NL > 0) {
     STAGE(a, s, launch_expand_bins(a, sorted_keys, sorted_gid, (uint32_t)NL, bshift, tile_m, bounds_done, lists,
@@ -1015,7 +997,7 @@ int wgsr_mark_visible(int P, const float* means3D, const float* viewmatrix, cons
                       uint8_t* present, void* stream) {
   g_err[0] = 0;
   if (P < 0) return set_error(WGSR_EINVAL, "negative point count");
-  HIPCHK(launch_mark_visible(P, means3D, viewmatrix, projmatrix, present, (hipStream_t)stream));
+  HIPCHK(launch_mark_visible(P, means3D, viewmatrix, present, (hipStream_t)stream));
   return WGSR_OK;
 }
 

@@ -383,7 +383,7 @@ __device__ __forceinline__ void render_bwd_quad_tile(
 }
 
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void k_render_bwd_quad(
-    const uint2* __restrict__ ranges, const uint32_t* __restrict__ order, bool global_order,
+    const uint2* __restrict__ ranges, const uint32_t* __restrict__ order,
     const uint32_t* __restrict__ meta, const uint32_t* __restrict__ lists_exact,
     const uint32_t* __restrict__ lists_bins, const float4* __restrict__ splat,
     const ListRec* __restrict__ lrec, const uint32_t* __restrict__ slot_start, int W, int H, int gx, int ntiles,
@@ -407,7 +407,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 8))) void
 #endif
   // where the forward left the tile lists (ImageLayout::meta)
   const uint32_t* __restrict__ point_g = meta[0] ? lists_bins : lists_exact;
-  const uint32_t tile = order[global_order ? blockIdx.x : xcd_remap(blockIdx.x, (uint32_t)ntiles)];
+  const uint32_t tile = order[xcd_remap(blockIdx.x, (uint32_t)ntiles)];
   const float bg0 = bg[0], bg1 = bg[1], bg2 = bg[2];
   if (bg0 == 0.f && bg1 == 0.f && bg2 == 0.f)  // (uniform)
     render_bwd_quad_tile<false>(tile, ranges, point_g, splat, lrec, slot_start, W, H, gx, bg0, bg1, bg2, final_Ts,
@@ -572,7 +572,7 @@ __device__ __forceinline__ uint64_t split_batch_pairs(uint64_t todo, uint32_t cf
 // vs 69.8-70.4 us at TUM scale and was removed in round 5.)
 constexpr int kSegBatches = 3, kSegCap = kSegBatches * kBatch;
 __global__ __launch_bounds__(256) void k_render_bwd_seg(
-    const uint2* __restrict__ ranges, const uint32_t* __restrict__ order, bool global_order,
+    const uint2* __restrict__ ranges, const uint32_t* __restrict__ order,
     const uint32_t* __restrict__ meta, const uint32_t* __restrict__ lists_exact,
     const uint32_t* __restrict__ lists_bins, const float4* __restrict__ splat,
     const ListRec* __restrict__ lrec, const uint32_t* __restrict__ slot_start, int W,
@@ -588,7 +588,7 @@ __global__ __launch_bounds__(256) void k_render_bwd_seg(
     return;
   }
   const uint32_t* __restrict__ point_g = meta[0] ? lists_bins : lists_exact;
-  const uint32_t tile = order[global_order ? blockIdx.x : xcd_remap(blockIdx.x, (uint32_t)ntiles)];
+  const uint32_t tile = order[xcd_remap(blockIdx.x, (uint32_t)ntiles)];
   const int t = threadIdx.x, w = t >> 6, lane = t & 63;
   const int tx = (int)(tile % gx), ty = (int)(tile / gx);
   const int qx0 = tx * kTile + (w & 1) * 8, qy0 = ty * kTile + (w >> 1) * 8;  // this wave's quadrant
@@ -1455,14 +1455,14 @@ hipError_t launch_render_bwd(const wgsr_raster_args& a, const uint2* ranges, con
   const char* env = getenv("WGSR_BWD_SPLIT_BELOW");  // read per launch: tests switch kernels
   const int split_below = env ? atoi(env) : kBwdSplitBelowTiles;
   if (nt < split_below) {
-    hipLaunchKernelGGL(k_render_bwd_seg, dim3(nt), dim3(256), 0, s, ranges, order, false, meta,
+    hipLaunchKernelGGL(k_render_bwd_seg, dim3(nt), dim3(256), 0, s, ranges, order, meta,
                        lists_exact, lists_bins,
                        at<float4>(geom, L.splat), at<ListRec>(geom, L.lrec),
                        at<uint32_t>(geom, L.slot_start), a.W, a.H, gx, nt, a.bg, final_T, n_contrib, dL_dcolor,
                        dL_ddepth, partial, pflag, at<uint8_t>(const_cast<void*>(geom), L.gflag), zero);
     return hipGetLastError();
   }
-  hipLaunchKernelGGL(k_render_bwd_quad, dim3(nt), dim3(64), 0, s, ranges, order, false, meta,
+  hipLaunchKernelGGL(k_render_bwd_quad, dim3(nt), dim3(64), 0, s, ranges, order, meta,
                      lists_exact, lists_bins,
                      at<float4>(geom, L.splat),
                      at<ListRec>(geom, L.lrec), at<uint32_t>(geom, L.slot_start), a.W,

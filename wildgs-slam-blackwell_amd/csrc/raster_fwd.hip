@@ -537,8 +537,9 @@ __device__ __forceinline__ uint32_t bin_mask_tab(int bx, int by, int x0, int y0,
 }
 
 // Sort bins, after the dual scan's block sums (packed_scan_blocks: bsum[b]
-// = exclusive prefix of (exact list length, bins touched) over the 256-rank
-// blocks in depth order): each 256-thread workgroup finishes the scan for its
+// = the sums of (exact list length, bins touched) over 256-rank block b in
+// depth order, bsup their 16-block sums): each 256-thread workgroup sums the
+// blocks before its own and finishes the scan for its
 // ranks (thread <-> rank) -- slot_start[g], the backward's record slots, and
 // the ranks' first bin pair -- zeroes the "record written" flags of its slots,
 // and every wave expands its 64 ranks' bin rectangles into (key, Gaussian)
@@ -587,7 +588,7 @@ __global__ __launch_bounds__(kDupScanThreads) void k_duplicate_bins(
   // below wait for the records only; vmcnt counts in order): the earlier
   // superblocks' sums plus the earlier blocks of its own superblock
   uint2 pre = make_uint2(0u, 0u);
-  if (bsup) {
+  {
     const uint32_t b = blockIdx.x, sb = b / kScanSupBlocks;
     for (uint32_t q = (uint32_t)t; q < sb; q += kDupScanThreads) {
       const uint2 x = bsup[(size_t)q * kScanSupStride];
@@ -599,8 +600,6 @@ __global__ __launch_bounds__(kDupScanThreads) void k_duplicate_bins(
       pre.x += x.x;
       pre.y += x.y;
     }
-  } else {
-    pre = bsum[blockIdx.x];
   }
   const uint32_t g = in ? g0 : 0u;
   if (!in) {
@@ -621,21 +620,15 @@ __global__ __launch_bounds__(kDupScanThreads) void k_duplicate_bins(
   }
   const uint32_t ic = wave_incl_scan(cnt), ib = wave_incl_scan(nb);
   if (lane == 63) s_w[w] = make_uint2(ic, ib);
-  uint2 wb;  // this block's first slot / first bin pair
-  if (bsup) {
-    pre.x = wave_sum_u32(pre.x);
-    pre.y = wave_sum_u32(pre.y);
-    if (lane == 0) s_p[w] = pre;
-    __syncthreads();
-    wb = make_uint2(0u, 0u);
+  pre.x = wave_sum_u32(pre.x);
+  pre.y = wave_sum_u32(pre.y);
+  if (lane == 0) s_p[w] = pre;
+  __syncthreads();
+  uint2 wb = make_uint2(0u, 0u);  // this block's first slot / first bin pair
 #pragma unroll
-    for (int k = 0; k < NW; ++k) {
-      wb.x += s_p[k].x;
-      wb.y += s_p[k].y;
-    }
-  } else {
-    __syncthreads();
-    wb = pre;
+  for (int k = 0; k < NW; ++k) {
+    wb.x += s_p[k].x;
+    wb.y += s_p[k].y;
   }
 #pragma unroll
   for (int k = 0; k < NW; ++k) {
@@ -833,10 +826,16 @@ __global__ __launch_bounds__(kExpThreads) void k_expand_bins(const uint32_t* __r
 // keys minus their minimum (R bits) are LSD-radix sorted in LDS, ceil(R / 9)
 // stable passes of <= 9-bit digits, each entry's position in the bin riding
 // along; the (key, Gaussian) pairs are then gathered in that order and cut
-// into the bin's per-tile lists (BdsEmit below; without it they go to the
-// spare key / payload buffers for k_expand_bins).  A bin of more than kBdsCap
-// entries runs the same passes chunk by chunk through global scratch (the
-// region behind the lists).
+// into the bin's per-tile lists (BdsEmit below), at every bin shift.  A bin of
+// more than kBdsCap entries runs the same passes chunk by chunk through global
+// scratch (the region behind the lists).
+// (The emit: each wave walks the sorted bin once for the tiles it owns,
+// bds_emit_walk.  4 x 4-tile bins, 1M / 1080p: k_bin_depth_sort 39.5 -> 50.1
+// us with k_expand_bins' 29.5 us and its launch gone, 0.7473 -> 0.7325 ms per
+// step; 2 x 2-tile bins (100k 512 x 384, the online loop): 0.1672 -> 0.1665
+// and 0.7223 -> 0.7199 ms.  The earlier lane <-> entry emit
+// (a count pass, a prefix over the waves, a write pass) lost to k_expand_bins
+// at 4 x 4 tiles (140.8 vs 131.3 us) and is gone.)
 // (512 threads, up to 10 entries per lane in steps of one: 1024 threads with
 // 1, 2, 4, 7 entries per lane measured 42-46 vs 33 us at 1M / 1080p)
 constexpr int kBdsThreads = 512, kBdsWaves = kBdsThreads / 64, kBdsItems = 10;
@@ -1013,6 +1012,7 @@ __device__ __forceinline__ uint32_t bds_excl_scan(uint32_t v, uint32_t* s_tmp, u
 constexpr int kBdsPosBits = 13, kBdsRankShift = kBdsPosBits + kBdsMaxBits;
 static_assert(kBdsCap <= (1 << kBdsPosBits) && kBdsItems * 64 <= (1 << (32 - kBdsRankShift)), "pk packing");
 __device__ __forceinline__ uint32_t bds_digit(uint32_t pk) { return (pk >> kBdsPosBits) & (kBdsDigits - 1); }
+__device__ __forceinline__ uint32_t bds_pos(uint32_t pk) { return pk & ((1u << kBdsPosBits) - 1u); }
 template <int JN>
 __device__ __forceinline__ void bds_rank(BdsLds& L, uint32_t cn, uint32_t mn, int shift, int bits,
                                          const uint32_t (&k)[JN], uint32_t (&pk)[JN]) {
@@ -1089,29 +1089,15 @@ __device__ __forceinline__ void bds_plan(int R, int& passes, int& pbits) {
   pbits = passes ? (R + passes - 1) / passes : 0;
 }
 
-// a bin of n <= 64 JN x kBdsWaves entries: wave w owns slots [w JN 64,
-// (w + 1) JN 64), JN entries per lane in registers, every pass ranked in LDS
+// The LDS passes over n <= 64 JN x kBdsWaves entries: wave w owns slots
+// [w JN 64, (w + 1) JN 64), JN entries per lane in registers, every pass
+// ranked in LDS.  k[j]: the key of slot (w JN + j) 64 + lane (anything past
+// n); on return bds_pos(pk[j]) is the input position of the entry sorted
+// into that slot (anything past n).
 template <int JN>
-__device__ __forceinline__ void bds_small(BdsLds& L, const uint32_t* __restrict__ skeys,
-                                          const uint32_t* __restrict__ sgid, const uint32_t* __restrict__ sdep,
-                                          const uint32_t* __restrict__ gdep, uint32_t lo, uint32_t n,
-                                          uint32_t* __restrict__ okeys, uint32_t* __restrict__ ogid, bool E,
-                                          const BdsEmit& EM) {
+__device__ __forceinline__ void bds_passes(BdsLds& L, uint32_t (&k)[JN], uint32_t (&pk)[JN], uint32_t n) {
   const int t = threadIdx.x, w = t >> 6, lane = t & 63;
-  constexpr uint32_t kPosMask = (1u << kBdsPosBits) - 1u;
-  uint32_t k[JN], pk[JN];
   uint32_t mn = 0xFFFFFFFFu, mx = 0u;
-  // (loads of clamped positions, all issued before any is used: a load under
-  // `le < n` is waited for at its join, one round trip per j)
-  if (gdep) {  // (uniform) the Gaussians' depth keys through the bin's ids: two round trips
-#pragma unroll
-    for (int j = 0; j < JN; ++j) k[j] = sgid[lo + min((uint32_t)(w * JN + j) * 64u + (uint32_t)lane, n - 1u)];
-#pragma unroll
-    for (int j = 0; j < JN; ++j) k[j] = gdep[k[j]];
-  } else {
-#pragma unroll
-    for (int j = 0; j < JN; ++j) k[j] = sdep[lo + min((uint32_t)(w * JN + j) * 64u + (uint32_t)lane, n - 1u)];
-  }
 #pragma unroll
   for (int j = 0; j < JN; ++j) {
     const uint32_t le = (uint32_t)(w * JN + j) * 64u + (uint32_t)lane;
@@ -1136,7 +1122,7 @@ __device__ __forceinline__ void bds_small(BdsLds& L, const uint32_t* __restrict_
 #pragma unroll
     for (int j = 0; j < JN; ++j) {
       const uint32_t le = (uint32_t)(w * JN + j) * 64u + (uint32_t)lane;
-      if (le < n) L.buf[bds_slot(L, pk[j])] = make_uint2(k[j], pk[j] & kPosMask);
+      if (le < n) L.buf[bds_slot(L, pk[j])] = make_uint2(k[j], bds_pos(pk[j]));
     }
     __syncthreads();
 #pragma unroll
@@ -1157,43 +1143,59 @@ __device__ __forceinline__ void bds_small(BdsLds& L, const uint32_t* __restrict_
     }
     __syncthreads();
   }
-  if (E) {  // the per-tile lists straight from the sorted bin
-    uint32_t m[JN], g[JN];
-    const uint32_t tmask = (1u << (1 << (2 * EM.bshift))) - 1u;
+}
+
+// a bin of n <= 64 JN x kBdsWaves entries: its depth keys gathered through
+// the Gaussian ids, the passes, then the per-tile lists straight from the
+// sorted bin
+template <int JN>
+__device__ __forceinline__ void bds_small(BdsLds& L, const uint32_t* __restrict__ skeys,
+                                          const uint32_t* __restrict__ sgid, const uint32_t* __restrict__ gdep,
+                                          uint32_t lo, uint32_t n, const BdsEmit& EM) {
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  uint32_t k[JN], pk[JN];
+  // (loads of clamped positions, all issued before any is used: a load under
+  // `le < n` is waited for at its join, one round trip per j; the Gaussians'
+  // depth keys through the bin's ids are two round trips)
 #pragma unroll
-    for (int j = 0; j < JN; ++j) {
-      const uint32_t le = (uint32_t)(w * JN + j) * 64u + (uint32_t)lane;
-      const uint32_t q = le < n ? pk[j] & kPosMask : 0u;  // (unconditional loads, as above)
-      m[j] = skeys[lo + q];
-      g[j] = sgid[lo + q];
-    }
+  for (int j = 0; j < JN; ++j) k[j] = sgid[lo + min((uint32_t)(w * JN + j) * 64u + (uint32_t)lane, n - 1u)];
 #pragma unroll
-    for (int j = 0; j < JN; ++j) {
-      const uint32_t le = (uint32_t)(w * JN + j) * 64u + (uint32_t)lane;
-      m[j] = le < n ? (m[j] >> 16) & tmask : 0u;
-      g[j] = le < n ? g[j] : 0u;
-    }
-    uint32_t run[2] = {0u, 0u};
-    bds_emit_chunk<JN>(L, m, g, n, 1 << (2 * EM.bshift), EM.lists + ((size_t)lo << (2 * EM.bshift)), n, run);
-    return;
-  }
-  // every gather load issued before the first store (unconditional, clamped)
-  uint32_t ok[JN], og[JN];
+  for (int j = 0; j < JN; ++j) k[j] = gdep[k[j]];
+  bds_passes<JN>(L, k, pk, n);
+  uint32_t m[JN], g[JN];
+  const uint32_t tmask = (1u << (1 << (2 * EM.bshift))) - 1u;
 #pragma unroll
   for (int j = 0; j < JN; ++j) {
     const uint32_t le = (uint32_t)(w * JN + j) * 64u + (uint32_t)lane;
-    const uint32_t q = le < n ? pk[j] & kPosMask : 0u;
-    pk[j] = q;
-    ok[j] = okeys ? skeys[lo + q] : 0u;  // (uniform; null: the stable argsort of k_argsort_small)
-    og[j] = sgid ? sgid[lo + q] : q;
+    const uint32_t q = le < n ? bds_pos(pk[j]) : 0u;  // (unconditional loads, as above)
+    m[j] = skeys[lo + q];
+    g[j] = sgid[lo + q];
   }
 #pragma unroll
   for (int j = 0; j < JN; ++j) {
     const uint32_t le = (uint32_t)(w * JN + j) * 64u + (uint32_t)lane;
-    if (le < n) {
-      if (okeys) okeys[lo + le] = ok[j];
-      ogid[lo + le] = og[j];
-    }
+    m[j] = le < n ? (m[j] >> 16) & tmask : 0u;
+    g[j] = le < n ? g[j] : 0u;
+  }
+  uint32_t run[2] = {0u, 0u};
+  bds_emit_chunk<JN>(L, m, g, n, 1 << (2 * EM.bshift), EM.lists + ((size_t)lo << (2 * EM.bshift)), n, run);
+}
+
+// the same passes on keys loaded directly: perm[i] = the position of the i-th
+// smallest key (k_argsort_small)
+template <int JN>
+__device__ __forceinline__ void bds_argsort(BdsLds& L, const uint32_t* __restrict__ keys, uint32_t n,
+                                            uint32_t* __restrict__ perm) {
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  uint32_t k[JN], pk[JN];
+  // (loads of clamped positions, all issued before any is used, as in bds_small)
+#pragma unroll
+  for (int j = 0; j < JN; ++j) k[j] = keys[min((uint32_t)(w * JN + j) * 64u + (uint32_t)lane, n - 1u)];
+  bds_passes<JN>(L, k, pk, n);
+#pragma unroll
+  for (int j = 0; j < JN; ++j) {
+    const uint32_t le = (uint32_t)(w * JN + j) * 64u + (uint32_t)lane;
+    if (le < n) perm[le] = bds_pos(pk[j]);
   }
 }
 
@@ -1239,8 +1241,7 @@ __device__ __forceinline__ void bds_emit_big(BdsLds& L, const uint32_t* __restri
 // (key, position) pairs ping-ponging through global scratch
 __device__ __forceinline__ void bds_big(BdsLds& L, const uint32_t* __restrict__ skeys, const uint32_t* __restrict__ sgid,
                                      const uint32_t* __restrict__ gdep, uint32_t lo, uint32_t n, uint32_t NL,
-                                     uint32_t* __restrict__ okeys, uint32_t* __restrict__ ogid, uint2* scratch,
-                                     bool E, const BdsEmit& EM) {
+                                     uint2* scratch, const BdsEmit& EM) {
   const int t = threadIdx.x, w = t >> 6, lane = t & 63;
   uint32_t mn = 0xFFFFFFFFu, mx = 0u;
   auto dep = [&](uint32_t e) { return gdep[sgid[lo + e]]; };
@@ -1254,14 +1255,7 @@ __device__ __forceinline__ void bds_big(BdsLds& L, const uint32_t* __restrict__ 
   bds_plan(R, passes, pbits);
   constexpr int JN = 7;  // (chunks of half the LDS tile: fewer registers)
   if (passes == 0) {
-    if (E) {
-      bds_emit_big<JN>(L, skeys, sgid, nullptr, lo, n, EM);
-      return;
-    }
-    for (uint32_t e = (uint32_t)t; e < n; e += kBdsThreads) {
-      okeys[lo + e] = skeys[lo + e];
-      ogid[lo + e] = sgid[lo + e];
-    }
+    bds_emit_big<JN>(L, skeys, sgid, nullptr, lo, n, EM);
     return;
   }
   constexpr uint32_t kChunk = JN * kBdsThreads;
@@ -1320,62 +1314,44 @@ __device__ __forceinline__ void bds_big(BdsLds& L, const uint32_t* __restrict__ 
     __syncthreads();
   }
   const uint2* fin = ((passes - 1) & 1) ? bufB : bufA;
-  if (E) {
-    bds_emit_big<JN>(L, skeys, sgid, fin, lo, n, EM);
-    return;
-  }
-  for (uint32_t e = (uint32_t)t; e < n; e += kBdsThreads) {
-    const uint32_t q = bds_load_scratch(fin + e).y;
-    okeys[lo + e] = skeys[lo + q];
-    ogid[lo + e] = sgid[lo + q];
-  }
+  bds_emit_big<JN>(L, skeys, sgid, fin, lo, n, EM);
+}
+
+// the smallest JN that holds the bin, else the chunked passes
+// (every step of JN: a bin's time is its busiest wave's chain of JN entry
+// groups per pass, and a coarser JN leaves the last waves idle -- measured
+// with 1024 threads: 4.7k entries at JN = 7 keep 11 of 16 waves busy, at
+// JN = 5 all 15 it needs)
+template <int JN = 1>
+__device__ __forceinline__ void bds_sort_bin(BdsLds& L, const uint32_t* __restrict__ skeys,
+                                             const uint32_t* __restrict__ sgid, const uint32_t* __restrict__ gdep,
+                                             uint32_t lo, uint32_t n, uint32_t NL, uint2* scratch, const BdsEmit& EM) {
+  if constexpr (JN > kBdsItems)
+    bds_big(L, skeys, sgid, gdep, lo, n, NL, scratch, EM);
+  else if (n <= (uint32_t)JN * kBdsThreads)
+    bds_small<JN>(L, skeys, sgid, gdep, lo, n, EM);
+  else
+    bds_sort_bin<JN + 1>(L, skeys, sgid, gdep, lo, n, NL, scratch, EM);
 }
 
 __global__ __launch_bounds__(kBdsThreads) void k_bin_depth_sort(
     const uint32_t* __restrict__ skeys, const uint32_t* __restrict__ sgid, const uint2* __restrict__ bounds,
-    const uint32_t* __restrict__ gdep, uint32_t NL,
-    uint32_t* __restrict__ okeys, uint32_t* __restrict__ ogid, uint2* scratch, BdsEmit emit) {
+    const uint32_t* __restrict__ gdep, uint32_t NL, uint2* scratch, BdsEmit emit) {
   __shared__ BdsLds L;
   const int t = threadIdx.x;
   const uint32_t bin = blockIdx.x;
   const uint2 bb = bounds[bin];
   const uint32_t lo = bb.x, n = bb.y - bb.x;
-  // (a flag, not a pointer to the by-value argument: that would put it in scratch)
-  const bool E = emit.lists != nullptr;
   if (n == 0) {  // block-uniform
-    if (E) bds_emit_ranges(L, emit, bin, lo, 0u);
+    bds_emit_ranges(L, emit, bin, lo, 0u);
     return;
   }
 #pragma unroll
   for (int q = 0; q < kBdsWaves; ++q)
     if (bds_owns_digit()) L.wcnt[q][t] = 0u;  // (published by bds_range's barrier)
   for (int i = t; i < kBdsWaves * kBdsDigits; i += kBdsThreads) (&L.match[0][0])[i] = 0ull;
-  if (n <= 1u * kBdsThreads)
-    bds_small<1>(L, skeys, sgid, nullptr, gdep, lo, n, okeys, ogid, E, emit);
-  else if (n <= 2u * kBdsThreads)
-    bds_small<2>(L, skeys, sgid, nullptr, gdep, lo, n, okeys, ogid, E, emit);
-  // (every step of JN: a bin's time is its busiest wave's chain of JN entry
-  // groups per pass, and a coarser JN leaves the last waves idle -- 4.7k
-  // entries at JN = 7 keep 11 of 16 waves busy, at JN = 5 all 15 it needs)
-  else if (n <= 3u * kBdsThreads)
-    bds_small<3>(L, skeys, sgid, nullptr, gdep, lo, n, okeys, ogid, E, emit);
-  else if (n <= 4u * kBdsThreads)
-    bds_small<4>(L, skeys, sgid, nullptr, gdep, lo, n, okeys, ogid, E, emit);
-  else if (n <= 5u * kBdsThreads)
-    bds_small<5>(L, skeys, sgid, nullptr, gdep, lo, n, okeys, ogid, E, emit);
-  else if (n <= 6u * kBdsThreads)
-    bds_small<6>(L, skeys, sgid, nullptr, gdep, lo, n, okeys, ogid, E, emit);
-  else if (n <= 7u * kBdsThreads)
-    bds_small<7>(L, skeys, sgid, nullptr, gdep, lo, n, okeys, ogid, E, emit);
-  else if (kBdsItems > 8 && n <= 8u * kBdsThreads)
-    bds_small<(kBdsItems > 8 ? 8 : 7)>(L, skeys, sgid, nullptr, gdep, lo, n, okeys, ogid, E, emit);
-  else if (kBdsItems > 9 && n <= 9u * kBdsThreads)
-    bds_small<(kBdsItems > 9 ? 9 : 7)>(L, skeys, sgid, nullptr, gdep, lo, n, okeys, ogid, E, emit);
-  else if (kBdsItems > 7 && n <= (uint32_t)kBdsCap)
-    bds_small<kBdsItems>(L, skeys, sgid, nullptr, gdep, lo, n, okeys, ogid, E, emit);
-  else
-    bds_big(L, skeys, sgid, gdep, lo, n, NL, okeys, ogid, scratch, E, emit);
-  if (E) bds_emit_ranges(L, emit, bin, lo, n);
+  bds_sort_bin(L, skeys, sgid, gdep, lo, n, NL, scratch, emit);
+  bds_emit_ranges(L, emit, bin, lo, n);
 }
 
 // ---- tile ranges and the tiles' launch order ---------------------------------
@@ -1398,20 +1374,19 @@ __device__ __forceinline__ void tile_chunk(uint32_t x, uint32_t nt, uint32_t& c0
 // Counting sort of the chunk's tiles by descending work bucket (one
 // 1024-thread workgroup per chunk; positions inside a bucket come from LDS
 // atomics, so ties may land in any order).
-// work of a tile: work[tile], or with quads the max of work[4 tile .. 4 tile + 3]
-__device__ __forceinline__ uint32_t tile_work(const uint32_t* __restrict__ work, bool quads, uint32_t tile) {
-  if (!quads) return work[tile];
+// work of a tile: the max of its quadrants' work[4 tile .. 4 tile + 3]
+__device__ __forceinline__ uint32_t tile_work(const uint32_t* __restrict__ work, uint32_t tile) {
   const uint4 q = reinterpret_cast<const uint4*>(work)[tile];
   return max(max(q.x, q.y), max(q.z, q.w));
 }
 
-__device__ __forceinline__ void order_chunk(uint32_t c0, uint32_t c1, const uint32_t* __restrict__ work, bool quads,
+__device__ __forceinline__ void order_chunk(uint32_t c0, uint32_t c1, const uint32_t* __restrict__ work,
                                             uint32_t* __restrict__ order, uint32_t* s_cnt) {
   const int t = threadIdx.x;
   s_cnt[t] = 0;
   __syncthreads();
   auto bucket = [&](uint32_t tile) {
-    return (uint32_t)(kOrderBuckets - 1) - min((uint32_t)(kOrderBuckets - 1), tile_work(work, quads, tile));
+    return (uint32_t)(kOrderBuckets - 1) - min((uint32_t)(kOrderBuckets - 1), tile_work(work, tile));
   };
   for (uint32_t tile = c0 + t; tile < c1; tile += 1024) atomicAdd(&s_cnt[bucket(tile)], 1u);
   __syncthreads();
@@ -1457,15 +1432,13 @@ __global__ __launch_bounds__(256) void k_ranges(const uint32_t* __restrict__ key
 
 // The backward's launch order by each tile's deepest contributor (its
 // back-to-front walk length), written by the forward.
-// One workgroup per XCD chunk, or (global) one for all tiles: then the
-// render kernel takes order[blockIdx] and round-robin dispatch deals every
-// 8th tile of the sorted list to each XCD.
-__global__ __launch_bounds__(1024) void k_tile_order(const uint32_t* __restrict__ work, bool quads, bool global,
-                                                     uint32_t ntiles, uint32_t* __restrict__ order) {
+// One workgroup per XCD chunk.
+__global__ __launch_bounds__(1024) void k_tile_order(const uint32_t* __restrict__ work, uint32_t ntiles,
+                                                     uint32_t* __restrict__ order) {
   __shared__ uint32_t s_cnt[kOrderBuckets];
-  uint32_t c0 = 0, c1 = ntiles;
-  if (!global) tile_chunk(blockIdx.x, ntiles, c0, c1);
-  order_chunk(c0, c1, work, quads, order, s_cnt);
+  uint32_t c0, c1;
+  tile_chunk(blockIdx.x, ntiles, c0, c1);
+  order_chunk(c0, c1, work, order, s_cnt);
 }
 
 // Splat records arrive 64 at a time through LDS; wave 0 loads the next
@@ -1941,7 +1914,7 @@ hipError_t launch_preprocess(const wgsr_raster_args& a, void* geom, int32_t* rad
 }
 
 hipError_t launch_duplicate_bins(const wgsr_raster_args& a, void* geom, const uint32_t* depth_order, int bshift,
-                                 uint8_t* pflag, uint32_t* keys, uint32_t* vals, bool bsup, const ZeroJob& zero,
+                                 uint8_t* pflag, uint32_t* keys, uint32_t* vals, const ZeroJob& zero,
                                  uint32_t* meta, hipStream_t s, uint32_t cap_slots, uint32_t cap_pairs) {
   if (a.P == 0) return hipSuccess;
   const GeomLayout L(a.P);
@@ -1950,22 +1923,31 @@ hipError_t launch_duplicate_bins(const wgsr_raster_args& a, void* geom, const ui
   hipLaunchKernelGGL(bshift == 1 ? k_duplicate_bins<1> : k_duplicate_bins<2>,
                      dim3((a.P + kDupScanThreads - 1) / kDupScanThreads), dim3(kDupScanThreads), 0,
                      s, (uint32_t)a.P, B.bx, at<ListRec>(geom, L.lrec), depth_order, at<uint2>(geom, L.bsum),
-                     bsup ? at<uint2>(geom, L.bsup) : nullptr,
-                     at<float4>(geom, L.splat),
+                     at<uint2>(geom, L.bsup), at<float4>(geom, L.splat),
                      at<uint32_t>(geom, L.slot_start), pflag, keys, vals, zero, meta, cap_slots, cap_pairs);
   return hipGetLastError();
 }
+
+namespace {
+// every bin's [start, end) in the NB bin-sorted keys, unless a one-pass sort
+// already wrote them (bounds_done)
+hipError_t make_bin_bounds(const uint32_t* sorted_keys, uint32_t NB, int nbins, uint2* bounds, bool bounds_done,
+                           hipStream_t s) {
+  if (bounds_done) return hipSuccess;
+  hipError_t e = hipMemsetAsync(bounds, 0, sizeof(uint2) * (size_t)nbins, s);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_bin_bounds, dim3((NB + 255) / 256), dim3(256), 0, s, sorted_keys, NB, bounds);
+  return hipSuccess;
+}
+}  // namespace
 
 hipError_t launch_expand_bins(const wgsr_raster_args& a, const uint32_t* sorted_keys, const uint32_t* sorted_g,
                               uint32_t NB, int bshift, uint2* bounds, bool bounds_done, uint32_t* lists, uint2* ranges,
                               uint32_t* tile_len, uint32_t* meta, hipStream_t s) {
   const int gx = (a.W + kTile - 1) / kTile, gy = (a.H + kTile - 1) / kTile;
   const Bins B(gx, gy, bshift);
-  if (!bounds_done) {  // (a one-pass sort already wrote them)
-    hipError_t e = hipMemsetAsync(bounds, 0, sizeof(uint2) * (size_t)B.n, s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_bin_bounds, dim3((NB + 255) / 256), dim3(256), 0, s, sorted_keys, NB, bounds);
-  }
+  hipError_t e = make_bin_bounds(sorted_keys, NB, B.n, bounds, bounds_done, s);
+  if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_expand_bins, dim3((uint32_t)B.n << bshift), dim3(kExpThreads), 0, s, sorted_keys, sorted_g, bounds, gx,
                      gy, bshift, B.bx, lists, ranges, tile_len, meta);
   return hipGetLastError();
@@ -1979,19 +1961,16 @@ __global__ __launch_bounds__(kBdsThreads) void k_argsort_small(const uint32_t* _
                                                               uint32_t* __restrict__ perm) {
   __shared__ BdsLds L;
   const int t = threadIdx.x;
-  const BdsEmit none{};
 #pragma unroll
   for (int q = 0; q < kBdsWaves; ++q)
     if (bds_owns_digit()) L.wcnt[q][t] = 0u;
   for (int i = t; i < kBdsWaves * kBdsDigits; i += kBdsThreads) (&L.match[0][0])[i] = 0ull;
-  if (kBdsThreads >= 1024 && n <= 1u * kBdsThreads)
-    bds_small<1>(L, nullptr, nullptr, keys, nullptr, 0u, n, nullptr, perm, false, none);
-  else if (n <= 2u * kBdsThreads)
-    bds_small<2>(L, nullptr, nullptr, keys, nullptr, 0u, n, nullptr, perm, false, none);
+  if (n <= 2u * kBdsThreads)
+    bds_argsort<2>(L, keys, n, perm);
   else if (n <= 4u * kBdsThreads)
-    bds_small<4>(L, nullptr, nullptr, keys, nullptr, 0u, n, nullptr, perm, false, none);
+    bds_argsort<4>(L, keys, n, perm);
   else
-    bds_small<kBdsItems>(L, nullptr, nullptr, keys, nullptr, 0u, n, nullptr, perm, false, none);
+    bds_argsort<kBdsItems>(L, keys, n, perm);
 }
 }  // namespace
 
@@ -2005,20 +1984,15 @@ hipError_t launch_argsort_small(const uint32_t* keys, uint32_t n, uint32_t* perm
 
 hipError_t launch_bin_depth_sort(const wgsr_raster_args& a, const uint32_t* sorted_keys, const uint32_t* sorted_g,
                                  uint32_t NB, int bshift, uint2* bounds, bool bounds_done, const uint32_t* gdepth,
-                                 uint32_t* okeys, uint32_t* ogid, void* scratch, hipStream_t s, uint32_t* lists,
-                                 uint2* ranges, uint32_t* tile_len, uint32_t* meta) {
+                                 void* scratch, uint32_t* lists, uint2* ranges, uint32_t* tile_len, uint32_t* meta,
+                                 hipStream_t s) {
   const int gx = (a.W + kTile - 1) / kTile, gy = (a.H + kTile - 1) / kTile;
   const Bins B(gx, gy, bshift);
-  if (!bounds_done) {  // (a one-pass sort already wrote them)
-    hipError_t e = hipMemsetAsync(bounds, 0, sizeof(uint2) * (size_t)B.n, s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_bin_bounds, dim3((NB + 255) / 256), dim3(256), 0, s, sorted_keys, NB, bounds);
-  }
-  // lists != null: the per-tile lists and ranges are emitted here (no
-  // k_expand_bins); else the sorted bins go to okeys / ogid
+  hipError_t e = make_bin_bounds(sorted_keys, NB, B.n, bounds, bounds_done, s);
+  if (e != hipSuccess) return e;
   const BdsEmit emit{lists, ranges, tile_len, meta, gx, gy, bshift, B.bx};
   hipLaunchKernelGGL(k_bin_depth_sort, dim3((uint32_t)B.n), dim3(kBdsThreads), 0, s, sorted_keys, sorted_g, bounds,
-                     gdepth, NB, okeys, ogid, static_cast<uint2*>(scratch), emit);
+                     gdepth, NB, static_cast<uint2*>(scratch), emit);
   return hipGetLastError();
 }
 
@@ -2041,7 +2015,7 @@ hipError_t launch_ranges(const uint32_t* sorted_keys, uint32_t N, int ntiles, ui
 
 hipError_t launch_tile_order(const uint32_t* work_quads, int ntiles, uint32_t* order, hipStream_t s) {
   // per-XCD chunks (one global LPT list measured 2 % slower)
-  hipLaunchKernelGGL(k_tile_order, dim3(8), dim3(1024), 0, s, work_quads, true, false, (uint32_t)ntiles, order);
+  hipLaunchKernelGGL(k_tile_order, dim3(8), dim3(1024), 0, s, work_quads, (uint32_t)ntiles, order);
   return hipGetLastError();
 }
 
@@ -2129,9 +2103,7 @@ hipError_t launch_check_tile_lists(const wgsr_raster_args& a, int bshift, uint64
   return hipGetLastError();
 }
 
-hipError_t launch_mark_visible(int P, const float* means3D, const float* view, const float* proj, uint8_t* present,
-                               hipStream_t s) {
-  (void)proj;
+hipError_t launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t s) {
   if (P == 0) return hipSuccess;
   hipLaunchKernelGGL(k_mark_visible, dim3((P + 255) / 256), dim3(256), 0, s, P, means3D, view, present);
   return hipGetLastError();

@@ -786,55 +786,11 @@ __global__ __launch_bounds__(256) void k_scan2_reduce(const uint32_t* __restrict
   uint2 tot;
   block_excl_scan256_2(acc, s_tmp, &tot);
   if (t == 0) {
-    bsum[blockIdx.x] = tot;
-    if (bsup) {  // (superblock mode: bsum keeps the raw block sums)
-      uint32_t* sp = reinterpret_cast<uint32_t*>(&bsup[(size_t)(blockIdx.x / kScanSupBlocks) * kScanSupStride]);
-      if (tot.x) atomicAdd(sp, tot.x);
-      if (tot.y) atomicAdd(sp + 1, tot.y);
-    }
+    bsum[blockIdx.x] = tot;  // (the raw block sum; its superblock's sum beside it)
+    uint32_t* sp = reinterpret_cast<uint32_t*>(&bsup[(size_t)(blockIdx.x / kScanSupBlocks) * kScanSupStride]);
+    if (tot.x) atomicAdd(sp, tot.x);
+    if (tot.y) atomicAdd(sp + 1, tot.y);
   }
-}
-
-// single workgroup of 1024 threads: exclusive scan of the nbs block sums in
-// place, total -> bsum[nbs].  Each thread owns a contiguous run of `per`
-// sums, loaded up front in chunks of 8 (independent loads in flight).
-__global__ __launch_bounds__(1024) void k_scan2_bsum(uint2* __restrict__ bsum, uint32_t nbs) {
-  constexpr int NW = 16;
-  __shared__ uint2 s_w[NW];
-  const int t = threadIdx.x, w = t >> 6, lane = t & 63;
-  const uint32_t per = (nbs + 1023) / 1024;
-  const uint32_t b0 = min(nbs, t * per), b1 = min(nbs, b0 + per);
-  uint2 acc = make_uint2(0u, 0u);
-  for (uint32_t b = b0; b < b1; b += 8) {
-    uint2 v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = b + u < b1 ? bsum[b + u] : make_uint2(0u, 0u);
-#pragma unroll
-    for (int u = 0; u < 8; ++u) { acc.x += v[u].x; acc.y += v[u].y; }
-  }
-  const uint32_t ia = wave_incl_scan(acc.x), ib = wave_incl_scan(acc.y);
-  if (lane == 63) s_w[w] = make_uint2(ia, ib);
-  __syncthreads();
-  uint2 run = make_uint2(ia - acc.x, ib - acc.y), tot = make_uint2(0u, 0u);
-#pragma unroll
-  for (int k = 0; k < NW; ++k) {
-    const uint2 x = s_w[k];
-    if (k < w) { run.x += x.x; run.y += x.y; }
-    tot.x += x.x;
-    tot.y += x.y;
-  }
-  for (uint32_t b = b0; b < b1; b += 8) {
-    uint2 v[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = b + u < b1 ? bsum[b + u] : make_uint2(0u, 0u);
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      if (b + u < b1) bsum[b + u] = run;
-      run.x += v[u].x;
-      run.y += v[u].y;
-    }
-  }
-  if (t == 0) bsum[nbs] = tot;
 }
 
 }  // namespace
@@ -1026,7 +982,6 @@ hipError_t packed_scan_blocks(const uint32_t* packed, uint32_t stride, const uin
   uint2* bs = static_cast<uint2*>(bsum);
   hipLaunchKernelGGL(k_scan2_reduce<kPackedScanTile / 256>, dim3(nbs), dim3(256), 0, stream, packed, stride, idx,
                      (uint32_t)n, bs, static_cast<uint2*>(bsup), pub);
-  if (!bsup) hipLaunchKernelGGL(k_scan2_bsum, dim3(1), dim3(1024), 0, stream, bs, nbs);
   return hipGetLastError();
 }
 

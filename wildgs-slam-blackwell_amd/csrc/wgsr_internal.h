@@ -8,15 +8,17 @@
 
 namespace wgsr {
 
-// Stable LSD radix sort on bits [begin_bit, end_bit) (8-bit digits, onesweep).
+// number of passes radix_sort_pairs makes over [begin_bit, end_bit) (the
+// result alternates buffers each pass)
+int radix_passes(int begin_bit, int end_bit);
+// Stable LSD radix sort on bits [begin_bit, end_bit): 8-bit digits, each pass
+// reduce-then-scan, or one wide pass for 9-10 bits.
 // Input in keys/vals (vals ignored if vals_iota: value = input position); the
 // result lands in keys_alt/vals_alt when *result_in_alt, else in keys/vals.
 // Scratch: status >= sort_status_bytes(n), totals >= kSortTotalsBytes.
-// number of passes radix_sort_pairs makes over [begin_bit, end_bit) (the
-// result alternates buffers each pass).  digit_bounds: when the sort runs as
-// one wide pass over bits [0, end_bit), each digit's [start, end) in the
-// sorted output is written there (*bounds_done = true).
-int radix_passes(int begin_bit, int end_bit);
+// digit_bounds: when the sort runs as one wide pass over bits [0, end_bit),
+// each digit's [start, end) in the sorted output is written there
+// (*bounds_done = true).
 // wide_threads: threads on each tile of a wide (9-10 bit) pass -- 256, 512 or
 // 1024; anything else: the default (kWideSortThreads on 4096-key tiles).
 hipError_t radix_sort_pairs(uint32_t* keys, uint32_t* keys_alt, uint32_t* vals, uint32_t* vals_alt, bool vals_iota,
@@ -46,25 +48,19 @@ hipError_t exclusive_scan_gather(const uint32_t* vals, const uint32_t* idx, size
                                  uint32_t* scatter_out, uint32_t* bsum, uint32_t* total_out, hipStream_t stream,
                                  uint32_t stride = 1);
 
-// First two steps of a scan of packed (lo 16 | hi 16) values gathered as
-// packed[idx[i]]: bsum[b] = exclusive prefix (lo sums, hi sums) of block b of
-// kScanTile elements, bsum[blocks] = totals.  bsum: 8 x (blocks + 1) bytes.
-// With bsup (zeroed, packed_scan_supers(n) uint2): bsum keeps the raw block
-// sums and bsup[s] the sums of blocks [16 s, 16 s + 16); no prefix pass.
-// The down-sweep is the caller's (k_scan_bins_down emits pairs).
-// packed[idx[i] * stride]: (lo 16 | hi 16 bits) pairs gathered through idx
+// First step of a scan of packed (lo 16 | hi 16) values gathered as
+// packed[idx[i] * stride]: bsum[b] = (lo sum, hi sum) of block b of
+// kPackedScanTile elements, and bsup[s] (zeroed by the caller,
+// packed_scan_supers(n) uint2) += the sums of blocks [16 s, 16 s + 16).
+// bsum: 8 x blocks bytes.  The prefix over them and the down-sweep are
+// the caller's (k_duplicate_bins emits pairs).
 hipError_t packed_scan_blocks(const uint32_t* packed, uint32_t stride, const uint32_t* idx, size_t n, void* bsum,
-                              hipStream_t stream,
-                              void* bsup = nullptr, const PublishJob& pub = PublishJob{});
+                              hipStream_t stream, void* bsup, const PublishJob& pub = PublishJob{});
 
 int num_bits(uint32_t n);  // bits needed to represent values in [0, n)
 
 // thread-local error message plumbing for the C ABI
 int set_error(int code, const char* fmt, ...);
-
-struct RasterGrid {
-  int gx, gy, ntiles;
-};
 
 // forward stages (raster_fwd.hip)
 // rect_pairs[0..kRectPairLanes) += upstream's num_rendered contributions (rect
@@ -83,26 +79,24 @@ hipError_t launch_cap_counts(const unsigned long long* partial, uint64_t cap_rec
 // the Gaussian index order (depth_order null), which k_gauss_bwd_compact
 // reads: then Gaussian g's slots are [slot_start[g], slot_start[g + 1]).
 hipError_t launch_duplicate_bins(const wgsr_raster_args& a, void* geom, const uint32_t* depth_order, int bshift,
-                                 uint8_t* pflag, uint32_t* keys, uint32_t* vals, bool bsup, const ZeroJob& zero,
+                                 uint8_t* pflag, uint32_t* keys, uint32_t* vals, const ZeroJob& zero,
                                  uint32_t* meta, hipStream_t s, uint32_t cap_slots = 0xFFFFFFFFu,
                                  uint32_t cap_pairs = 0xFFFFFFFFu);
 hipError_t launch_duplicate(const wgsr_raster_args& a, const void* geom, const uint32_t* sorted_g, uint32_t P,
                             uint32_t* keys, uint32_t* slot_g, uint8_t* pflag, hipStream_t s);
-// per-bin depth sort (pairs duplicated in index order): every bin's entries
-// stably by depth key (gdepth: the Gaussians' depth keys, gathered through
-// each bin's Gaussian ids)
-// (bounds written first unless bounds_done); scratch: >= 2 NB uint2 (bins
-// beyond one LDS tile).  With lists: the per-tile exact lists, ranges,
-// tile_len and meta emitted straight from each sorted bin (what
-// launch_expand_bins would make of it); else the sorted bins -> okeys / ogid.
 // stable argsort of n <= argsort_small_max() keys in one workgroup (perm: positions)
 uint32_t argsort_small_max();
 hipError_t launch_argsort_small(const uint32_t* keys, uint32_t n, uint32_t* perm, hipStream_t s);
+// per-bin depth sort (pairs duplicated in index order): every bin's entries
+// stably by depth key (gdepth: the Gaussians' depth keys, gathered through
+// each bin's Gaussian ids; bounds written first unless bounds_done), then the
+// per-tile exact lists, ranges, tile_len and meta straight from each sorted
+// bin (what launch_expand_bins would make of it).  scratch: >= 2 NB uint2
+// (bins beyond one LDS tile).
 hipError_t launch_bin_depth_sort(const wgsr_raster_args& a, const uint32_t* sorted_keys, const uint32_t* sorted_g,
                                  uint32_t NB, int bshift, uint2* bounds, bool bounds_done, const uint32_t* gdepth,
-                                 uint32_t* okeys, uint32_t* ogid, void* scratch, hipStream_t s,
-                                 uint32_t* lists = nullptr, uint2* ranges = nullptr, uint32_t* tile_len = nullptr,
-                                 uint32_t* meta = nullptr);
+                                 void* scratch, uint32_t* lists, uint2* ranges, uint32_t* tile_len, uint32_t* meta,
+                                 hipStream_t s);
 // per-tile exact lists out of the bin-sorted pairs: ranges / tile_len per
 // tile, the lists in bin-sized regions of `lists` (2^2s x NB entries)
 hipError_t launch_expand_bins(const wgsr_raster_args& a, const uint32_t* sorted_keys, const uint32_t* sorted_g,
@@ -122,8 +116,7 @@ hipError_t launch_zero_u32(uint32_t* p, size_t n, hipStream_t s);
 // wgsr_check_tile_lists' kernel (lists region sizes from num_rendered and the bin shift)
 hipError_t launch_check_tile_lists(const wgsr_raster_args& a, int bshift, uint64_t num_rendered, const void* binning,
                                    const void* image, uint32_t* bad, hipStream_t s);
-hipError_t launch_mark_visible(int P, const float* means3D, const float* view, const float* proj, uint8_t* present,
-                               hipStream_t s);
+hipError_t launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t s);
 
 // backward stages (raster_bwd.hip)
 // the tile lists: lists_bins when the forward's ImageLayout::meta word says so, else lists_exact

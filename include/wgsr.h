@@ -910,6 +910,50 @@ int wgsr_droid_ba_system(const float* poses, const float* disps, const float* in
                          float ep, int motion_only, void* workspace, int64_t workspace_bytes, double* H, double* g,
                          float* C, float* w, float* dx, uint32_t* status, void* stream);
 
+/* ---- lietorch's SE3 (csrc/lie.hip; python/lietorch).  A group element is 7
+ * floats (tx, ty, tz, qx, qy, qz, qw), a tangent vector 6 floats (tau, phi),
+ * translation part first; fp32, device memory, inference only. */
+#define WGSR_LIE_EXP 0    /* a: tangent [.., 6]            -> element [.., 7]  */
+#define WGSR_LIE_LOG 1    /* a: element                    -> tangent [.., 6]  */
+#define WGSR_LIE_INV 2    /* a: element                    -> element          */
+#define WGSR_LIE_MUL 3    /* a, b: elements                -> a b              */
+#define WGSR_LIE_ACT3 4   /* a: element, b: point [.., 3]  -> R b + t          */
+#define WGSR_LIE_ACT4 5   /* b: (X, Y, Z, w) [.., 4]       -> (R XYZ + w t, w) */
+#define WGSR_LIE_MATRIX 6 /* a: element                    -> 4 x 4 row-major  */
+#define WGSR_LIE_ADJ 7    /* b: tangent                    -> Adj b            */
+#define WGSR_LIE_ADJT 8   /* b: tangent                    -> Adj^T b          */
+#define WGSR_LIE_RETR 9   /* b: tangent                    -> exp(b) a         */
+/* One group operation on n output elements, one launch on `stream`, with no
+ * allocation and no synchronisation.  Output element e reads a's element
+ * e / inner_a and b's element e / inner_b (inner >= 1; b is ignored by the
+ * one-operand ops): an operand broadcast over trailing dimensions is passed
+ * as it is.  Adj = [[R, [t]x R], [0, R]].  Quaternions are not renormalised;
+ * log accepts either sign of q.  exp(0) is exactly (0, 0, 0, 0, 0, 0, 1),
+ * log of the identity exactly 0, X * identity exactly X. */
+int wgsr_lie_se3(int op, const float* a, int64_t inner_a, const float* b, int64_t inner_b, float* out, int64_t n,
+                 void* stream);
+
+#define WGSR_REPROJECT_JACOBIAN 1
+#define WGSR_REPROJECT_DEPTH 2
+/* projective_ops.projective_transform (DepthVideo.reproject) in one launch:
+ * for edge e and pixel (u, v) of frame i = ii[e] with disparity d, X0 =
+ * ((u - cx_i) / fx_i, (v - cy_i) / fy_i, 1, d), (X, Y, Z, d) = G_ij X0 with
+ * G_ij = G_j G_i^-1 (i == j: the stereo transform t = (-0.1, 0, 0), R = I),
+ * coords [n, ht, wd, 2] = (fx_j X / Z' + cx_j, fy_j Y / Z' + cy_j) with Z' =
+ * 1 where Z < 0.1 and Z elsewhere; valid [n, ht, wd, 1] = 1.0 where Z > 0.2
+ * (the Python's MIN_DEPTH, not the CUDA kernels' 0.25), else 0.0.
+ * intrinsics: [num, 4] with per_frame_intrinsics != 0, else one [4].
+ * flags & WGSR_REPROJECT_DEPTH: coords is [n, ht, wd, 3] with d / Z' third.
+ * flags & WGSR_REPROJECT_JACOBIAN: Jj [n, ht, wd, 2, 6] = d coords / d (left
+ * perturbation of G_j), Ji = -Adj^T_Gij applied to Jj's rows, Jz [n, ht, wd,
+ * 2, 1] = d coords / d d; without the flag the three must be null.  coords
+ * (two-slot form) and Jz 8-byte, Ji and Jj 16-byte aligned.  An edge with an
+ * index outside [0, num) reads nothing and gets NaN.  No allocation, no
+ * synchronisation; every output element is written. */
+int wgsr_droid_reproject(const float* poses, const float* disps, const float* intrinsics, int per_frame_intrinsics,
+                         int num, int ht, int wd, const int64_t* ii, const int64_t* jj, int n, int flags,
+                         float* coords, float* valid, float* Ji, float* Jj, float* Jz, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -326,6 +326,11 @@ def load():
         L.wgsr_droid_ba_system.restype = c_int
         L.wgsr_droid_ba_system.argtypes = ([_fp] * 9 + [c_int] * 7 + [ctypes.c_float] * 2 + [c_int]
                                            + [_fp, ctypes.c_int64] + [_fp] * 7)
+        # lietorch's SE3 and the fused reprojection (csrc/lie.hip)
+        L.wgsr_lie_se3.restype = c_int
+        L.wgsr_lie_se3.argtypes = [c_int, _fp, c_i64, _fp, c_i64, _fp, c_i64, _fp]
+        L.wgsr_droid_reproject.restype = c_int
+        L.wgsr_droid_reproject.argtypes = [_fp] * 3 + [c_int] * 4 + [_fp, _fp, c_int, c_int] + [_fp] * 5 + [_fp]
         L.wgsr_last_error.restype = ctypes.c_char_p
         L.wgsr_last_error.argtypes = []
         L.wgsr_version.restype = ctypes.c_char_p
@@ -370,6 +375,7 @@ EXPORTED_SYMBOLS = (
     "wgsr_droid_corr_index_forward", "wgsr_droid_corr_index_backward",
     "wgsr_droid_altcorr_forward", "wgsr_droid_altcorr_backward",
     "wgsr_droid_ba_workspace_bytes", "wgsr_droid_ba", "wgsr_droid_ba_system", "wgsr_droid_ba_stage_events",
+    "wgsr_lie_se3", "wgsr_droid_reproject",
 )
 
 VIEW_RECORD_FLOATS = 12   # WGSR_VIEW_RECORD_FLOATS

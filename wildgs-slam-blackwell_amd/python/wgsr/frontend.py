@@ -10,6 +10,9 @@
 * ``AltCorrBlock``      the correlation lookups of FactorGraph.update_lowmem
                         (corr.py AltCorrBlock), one fused launch per pyramid
                         level (csrc/droid_altcorr.hip)
+* ``reproject``         DepthVideo.reproject / projective_ops.projective_transform
+                        (projective_ops.py:110-139), one fused launch
+                        (csrc/lie.hip) instead of the composition of group ops
 
 poses [num, 7] = (tx, ty, tz, qx, qy, qz, qw), world to camera; disps
 [num, ht, wd]; intrinsics [4] = (fx, fy, cx, cy); device fp32 tensors.
@@ -20,8 +23,10 @@ import torch
 import torch.nn.functional as F
 
 import droid_backends
+from wgsr import _lib
 
 MIN_VALID_DEPTHS = 100  # mapper.py:593
+REPROJECT_JACOBIAN, REPROJECT_DEPTH = 1, 2  # WGSR_REPROJECT_* (include/wgsr.h)
 
 
 def distance(poses, disps, intrinsics, ii=None, jj=None, beta=0.3, bidirectional=True):
@@ -108,6 +113,64 @@ def ba(poses, disps, intrinsics, target, weight, eta, ii, jj, t0=1, t1=None, ite
                             motion_only, False)
     disps.clamp_(min=1e-5)
     return out
+
+
+@torch.no_grad()
+def reproject(poses, disps, intrinsics, ii, jj, jacobian=False, return_depth=False, check=True):
+    """projective_ops.projective_transform on the video buffers: ``poses``
+    [num, 7], ``disps`` [num, ht, wd], ``intrinsics`` [num, 4] (or one [4]),
+    ``ii`` / ``jj`` [E] int64, all on the device.  Returns the reference's
+    shapes: ``coords`` [1, E, ht, wd, 2] (3 with ``return_depth``: disparity
+    over depth in the third slot), ``valid`` [1, E, ht, wd, 1] (0 / 1 floats,
+    depth > 0.2) and, with ``jacobian``, ``(Ji, Jj, Jz)`` [1, E, ht, wd, 2, 6 |
+    6 | 1].  ``check`` reads ``ii.max()`` / ``jj.max()`` on the host and raises
+    for an index outside [0, num); with ``check=False`` there is no host read
+    (the call can be captured in a graph) and such an edge's outputs are NaN."""
+    droid_backends._contiguous(poses=poses, disps=disps, intrinsics=intrinsics, ii=ii, jj=jj)
+    dev = droid_backends._device_of(poses=poses, disps=disps, intrinsics=intrinsics, ii=ii, jj=jj)
+    if poses.dim() != 2 or poses.size(1) != 7:
+        raise RuntimeError("poses must have dimensions (num, 7)")
+    if disps.dim() != 3:
+        raise RuntimeError("disps must have dimensions (num, ht, wd)")
+    num, ht, wd = min(poses.size(0), disps.size(0)), disps.size(1), disps.size(2)
+    per_frame = intrinsics.dim() == 2
+    if per_frame:
+        if intrinsics.size(1) != 4:
+            raise RuntimeError("intrinsics must have dimensions (num, 4) or (4,)")
+        num = min(num, intrinsics.size(0))
+    elif tuple(intrinsics.shape) != (4,):
+        raise RuntimeError("intrinsics must have dimensions (num, 4) or (4,)")
+    for name, t in (("poses", poses), ("disps", disps), ("intrinsics", intrinsics)):
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"{name} must be float32")
+    droid_backends._index("ii", ii)
+    droid_backends._index("jj", jj)
+    if ii.numel() != jj.numel():
+        raise RuntimeError("ii and jj must have the same length")
+    E = ii.numel()
+    coords = torch.empty(1, E, ht, wd, 3 if return_depth else 2, dtype=torch.float32, device=dev)
+    valid = torch.empty(1, E, ht, wd, 1, dtype=torch.float32, device=dev)
+    Ji = Jj = Jz = None
+    if jacobian:
+        Ji = torch.empty(1, E, ht, wd, 2, 6, dtype=torch.float32, device=dev)
+        Jj = torch.empty_like(Ji)
+        Jz = torch.empty(1, E, ht, wd, 2, 1, dtype=torch.float32, device=dev)
+    if E and coords.numel():
+        if check:
+            lo = int(min(ii.min().item(), jj.min().item()))
+            hi = int(max(ii.max().item(), jj.max().item()))
+            if lo < 0 or hi >= num:
+                raise RuntimeError(f"ii / jj must index frames [0, {num}): got values in [{lo}, {hi}]")
+        flags = (REPROJECT_JACOBIAN if jacobian else 0) | (REPROJECT_DEPTH if return_depth else 0)
+        L = _lib.load()
+        with torch.cuda.device(dev):
+            _lib.check(L.wgsr_droid_reproject(poses.data_ptr(), disps.data_ptr(), intrinsics.data_ptr(),
+                                              int(per_frame), num, ht, wd, ii.data_ptr(), jj.data_ptr(), E, flags,
+                                              coords.data_ptr(), valid.data_ptr(), _lib.ptr(Ji), _lib.ptr(Jj),
+                                              _lib.ptr(Jz), _lib.stream_handle(dev)))
+    if jacobian:
+        return coords, valid, (Ji, Jj, Jz)
+    return coords, valid
 
 
 class AltCorrBlock:

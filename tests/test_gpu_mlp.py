@@ -6,7 +6,8 @@ wgsr.mlp.dropout_mask).  Tolerances: outputs rel 1e-5, parameter gradients
 rel-L1 1e-5 (fp32 reduction order differs from hipBLASLt's)."""
 import pytest
 import torch
-import torch.nn.functional as F
+
+from _loss_elementwise_ref import torch_mlp as _torch_mlp
 
 pytestmark = pytest.mark.gpu
 
@@ -16,19 +17,6 @@ DEV = torch.device("cuda:0")
 def _rel(a, b):
     a, b = a.detach().double().cpu(), b.detach().double().cpu()
     return float((a - b).abs().sum() / b.abs().sum().clamp_min(1e-30))
-
-
-def _torch_mlp(net, x, masks=None, p=0.0):
-    """MLPNetwork.forward with explicit dropout masks (torch's dropout:
-    x * mask / (1 - p))."""
-    H, W, C = x.shape[-3:]
-    y = x.reshape(-1, C)
-    for i, layer in enumerate(net.layers):
-        y = F.relu(F.linear(y, layer.weight, layer.bias))
-        if masks is not None:
-            y = y * masks[i] * (1.0 / (1.0 - p))
-    y = F.softplus(F.linear(y, net.output_layer.weight, net.output_layer.bias))
-    return y.view(x.shape[:-1])
 
 
 @pytest.mark.parametrize("shape,p", [((27, 36, 384), 0.0), ((77, 137, 384), 0.0), ((2, 9, 13, 128), 0.0),

@@ -864,6 +864,41 @@ int wgsr_droid_altcorr_backward(const float* fmap1, const float* fmap2, const fl
                                 int b, int n, int h1, int w1, int h2, int w2, int c, int radius, float* fmap1_grad,
                                 float* fmap2_grad, float* coords_grad, void* stream);
 
+/* ---- The all-pairs correlation pyramid of the frontend and the motion filter
+ * (CorrBlock, corr.py:39-90; csrc/droid_corrvol.hip; wgsr.frontend.CorrBlock).
+ * The volumes live in a store of `capacity` slots, one device allocation, 16-
+ * byte aligned.  A slot holds one edge's `levels` planes back to back: level
+ * i is [h, w, h >> i, w >> i] fp16, each level starting on a 16-byte
+ * boundary.  levels in [1, 4]; h and w each at least 2^(levels-1).  `dtype`
+ * is the volume's element type: only WGSR_DTYPE_F16 is built, and
+ * WGSR_DTYPE_F32 is refused with an error that names it.  Neither launch
+ * reads anything on the host: both can be captured in a graph. */
+/* bytes of one slot (a multiple of 16); -1 (and wgsr_last_error) for shapes
+ * the two calls below would refuse */
+int64_t wgsr_droid_corr_slot_bytes(int h, int w, int levels);
+/* Builds n edges in one launch: fmap1, fmap2 [n, c, h, w] fp16 contiguous
+ * (channel-major, as the reference holds them), c a positive multiple of 32;
+ * edge e goes to slot slots[e] (device int32 [n]; a slot outside [0, capacity)
+ * writes nothing).  Level 0 [p1, p2] = round_fp16(1/16 x the fp32-accumulated
+ * dot product of fmap1[:, p1] and fmap2[:, p2]): the reference's matmul of
+ * both maps / 4 under autocast.  Level i + 1 = round_fp16 of the mean of the
+ * 2 x 2 block of level i's stored fp16 values (avg_pool2d of what was stored,
+ * an odd trailing row or column dropped).  The pooled levels come from the
+ * workgroup's tile on chip: no plane is read back from memory.  16-byte moves
+ * when w is a multiple of 8 and the maps are 16-byte aligned, element moves
+ * otherwise.  n <= 65535. */
+int wgsr_droid_corr_build(const void* fmap1, const void* fmap2, int dtype, int n, int c, int h, int w, int levels,
+                          void* store, int capacity, const int32_t* slots, void* stream);
+/* Looks up every level of n edges in one launch: coords [n, h, w, 2] fp32 (x,
+ * y) as the caller holds them; corr [n, levels (2r+1)^2, h, w] fp16, channels
+ * [i (2r+1)^2, (i+1) (2r+1)^2) = wgsr_droid_corr_index_forward of level i of
+ * slot slots[e] at coords / 2^i (the scaling is exact and done in the
+ * kernel), bit for bit.  Every output element is written (no zero fill); an
+ * edge whose slot lies outside [0, capacity) reads nothing and gets NaN.
+ * radius <= 6. */
+int wgsr_droid_corr_lookup(const void* store, int capacity, const int32_t* slots, const float* coords, int dtype,
+                           int n, int h, int w, int levels, int radius, void* corr, void* stream);
+
 /* ---- droid_backends.ba (csrc/droid_ba.hip): DROID-SLAM's dense bundle
  * adjustment over n_edges edges (ii[e], jj[e]) with targets / weights
  * [n_edges, 2, ht, wd].  Frames [t0, t1) have free poses (P = t1 - t0); the

@@ -315,6 +315,13 @@ def load():
                                                  + [_fp])
         L.wgsr_droid_altcorr_backward.restype = c_int
         L.wgsr_droid_altcorr_backward.argtypes = [_fp] * 4 + [c_int] * 8 + [_fp] * 4
+        # wgsr.frontend.CorrBlock (csrc/droid_corrvol.hip)
+        L.wgsr_droid_corr_slot_bytes.restype = ctypes.c_int64
+        L.wgsr_droid_corr_slot_bytes.argtypes = [c_int] * 3
+        L.wgsr_droid_corr_build.restype = c_int
+        L.wgsr_droid_corr_build.argtypes = [_fp, _fp] + [c_int] * 6 + [_fp, c_int, _fp, _fp]
+        L.wgsr_droid_corr_lookup.restype = c_int
+        L.wgsr_droid_corr_lookup.argtypes = [_fp, c_int, _fp, _fp] + [c_int] * 6 + [_fp, _fp]
         # droid_backends.ba (csrc/droid_ba.hip)
         L.wgsr_droid_ba_workspace_bytes.restype = ctypes.c_int64
         L.wgsr_droid_ba_workspace_bytes.argtypes = [c_int] * 7
@@ -374,6 +381,7 @@ EXPORTED_SYMBOLS = (
     "wgsr_droid_frame_distance", "wgsr_droid_depth_filter", "wgsr_droid_iproj",
     "wgsr_droid_corr_index_forward", "wgsr_droid_corr_index_backward",
     "wgsr_droid_altcorr_forward", "wgsr_droid_altcorr_backward",
+    "wgsr_droid_corr_slot_bytes", "wgsr_droid_corr_build", "wgsr_droid_corr_lookup",
     "wgsr_droid_ba_workspace_bytes", "wgsr_droid_ba", "wgsr_droid_ba_system", "wgsr_droid_ba_stage_events",
     "wgsr_lie_se3", "wgsr_droid_reproject",
 )

@@ -10,6 +10,11 @@
 * ``AltCorrBlock``      the correlation lookups of FactorGraph.update_lowmem
                         (corr.py AltCorrBlock), one fused launch per pyramid
                         level (csrc/droid_altcorr.hip)
+* ``CorrBlock``         the all-pairs correlation pyramid of the frontend's local
+                        graph and the motion filter (corr.py CorrBlock): the
+                        volume and its pooled levels in one launch into the
+                        slots of a store, every level looked up in one launch
+                        (csrc/droid_corrvol.hip)
 * ``reproject``         DepthVideo.reproject / projective_ops.projective_transform
                         (projective_ops.py:110-139), one fused launch
                         (csrc/lie.hip) instead of the composition of group ops
@@ -18,6 +23,8 @@ poses [num, 7] = (tx, ty, tz, qx, qy, qz, qw), world to camera; disps
 [num, ht, wd]; intrinsics [4] = (fx, fy, cx, cy); device fp32 tensors.
 """
 from __future__ import annotations
+
+import heapq
 
 import torch
 import torch.nn.functional as F
@@ -239,3 +246,262 @@ class AltCorrBlock:
         if samples:
             return out.view(B, E, S, -1, H, W).permute(0, 1, 3, 4, 5, 2).contiguous()
         return out.view(B, E, -1, H, W)
+
+
+# ---------------------------------------------------------------------------
+# CorrBlock: the all-pairs correlation pyramid, held in slots
+# ---------------------------------------------------------------------------
+CORR_MAX_LEVELS = 4  # kCvMaxLevels (csrc/droid_corrvol.hip)
+
+
+def corr_slot_layout(h, w, num_levels):
+    """(offsets, elems): the first fp16 element of each level in a slot and
+    the elements per slot; every level starts on a 16-byte boundary
+    (``wgsr_droid_corr_slot_bytes``)."""
+    offsets, at = [], 0
+    for i in range(num_levels):
+        offsets.append(at)
+        at += h * w * (h >> i) * (w >> i)
+        at = (at + 7) & ~7
+    return offsets, at
+
+
+class SlotTable:
+    """The bookkeeping of a slot store, on the host and without a device: the
+    free list and the table edge -> slot, in edge order.  Free slots are taken
+    lowest first; a full store grows by doubling."""
+
+    def __init__(self, capacity):
+        if capacity < 1:
+            raise ValueError("a slot store needs a capacity of at least 1")
+        self.capacity = int(capacity)
+        self.slots = []                       # slot of edge k
+        self._free = list(range(self.capacity))  # a heap
+
+    def __len__(self):
+        return len(self.slots)
+
+    @property
+    def free(self):
+        return len(self._free)
+
+    def grow(self, need):
+        """Double the capacity until ``need`` slots are free."""
+        while len(self._free) < need:
+            for s in range(self.capacity, 2 * self.capacity):
+                heapq.heappush(self._free, s)
+            self.capacity *= 2
+        return self.capacity
+
+    def take(self, n):
+        """n free slots (growing first if need be), appended to the table as
+        the slots of n new edges."""
+        self.grow(n)
+        new = [heapq.heappop(self._free) for _ in range(n)]
+        self.slots.extend(new)
+        return new
+
+    def release(self, slots):
+        for s in slots:
+            heapq.heappush(self._free, s)
+
+    def select(self, index):
+        """``table = table[index]`` for whatever indexes dimension 0 of a
+        tensor (a boolean mask, an integer tensor, a slice); the slots no edge
+        holds any more go back to the free list."""
+        if isinstance(index, torch.Tensor):
+            index = index.cpu()  # (a device mask: the one host read)
+        kept = torch.tensor(self.slots, dtype=torch.int64)[index].reshape(-1).tolist()
+        self.release(sorted(set(self.slots) - set(kept)))
+        self.slots = kept
+        return list(kept)
+
+
+def _corr_geometry(store, slots, h, w, num_levels):
+    L = _lib.load()
+    slot_bytes = L.wgsr_droid_corr_slot_bytes(h, w, num_levels)
+    if slot_bytes < 0:
+        _lib.check(1)
+    if store.dtype != torch.float16 or store.dim() != 1 or not store.is_contiguous():
+        raise RuntimeError("the store must be a contiguous 1-D float16 tensor")
+    if slots.dtype != torch.int32 or slots.dim() != 1 or not slots.is_contiguous():
+        raise RuntimeError("slots must be a contiguous 1-D int32 tensor")
+    return L, store.numel() // (slot_bytes // 2)
+
+
+@torch.no_grad()
+def corr_build(fmap1, fmap2, store, slots, num_levels=4):
+    """Build the pyramids of n edges, ``fmap1`` / ``fmap2`` [n, C, H, W]
+    float16, into slots ``slots`` [n] (device int32) of ``store`` (1-D
+    float16, a whole number of slots): one launch, nothing read on the host."""
+    droid_backends._contiguous(fmap1=fmap1, fmap2=fmap2)
+    dev = droid_backends._device_of(fmap1=fmap1, fmap2=fmap2, store=store, slots=slots)
+    if fmap1.dim() != 4 or fmap1.shape != fmap2.shape:
+        raise RuntimeError("fmap1 and fmap2 must have the same dimensions (n, C, H, W)")
+    if fmap1.dtype != torch.float16 or fmap2.dtype != torch.float16:
+        raise NotImplementedError(f"corr_build: only float16 maps are built, got {fmap1.dtype} / {fmap2.dtype}")
+    n, c, h, w = fmap1.shape
+    L, capacity = _corr_geometry(store, slots, h, w, num_levels)
+    if slots.numel() != n:
+        raise RuntimeError("slots must name one slot per edge")
+    with torch.cuda.device(dev):
+        _lib.check(L.wgsr_droid_corr_build(fmap1.data_ptr(), fmap2.data_ptr(), droid_backends._DTYPE_TAG[fmap1.dtype],
+                                           n, c, h, w, num_levels, store.data_ptr(), capacity, slots.data_ptr(),
+                                           _lib.stream_handle(dev)))
+
+
+@torch.no_grad()
+def corr_lookup(store, slots, coords, num_levels=4, radius=3):
+    """corr [n, num_levels (2r+1)^2, H, W] float16 of ``coords`` [n, H, W, 2]
+    float32 (x, y): every level of the edges in ``slots`` in one launch."""
+    droid_backends._contiguous(coords=coords)
+    dev = droid_backends._device_of(store=store, slots=slots, coords=coords)
+    if coords.dim() != 4 or coords.size(3) != 2 or coords.dtype != torch.float32:
+        raise RuntimeError("coords must be a float32 tensor of dimensions (n, H, W, 2)")
+    n, h, w, _ = coords.shape
+    L, capacity = _corr_geometry(store, slots, h, w, num_levels)
+    if slots.numel() != n:
+        raise RuntimeError("slots must name one slot per edge")
+    r = int(radius)
+    out = torch.empty(n, num_levels * (2 * r + 1) ** 2, h, w, dtype=torch.float16, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.wgsr_droid_corr_lookup(store.data_ptr(), capacity, slots.data_ptr(), coords.data_ptr(),
+                                            droid_backends._DTYPE_TAG[store.dtype], n, h, w, num_levels, r,
+                                            out.data_ptr(), _lib.stream_handle(dev)))
+    return out
+
+
+class CorrBlock:
+    """The reference's ``CorrBlock`` (corr.py:39-90) for inference, as the
+    frontend's factor graph and the motion filter use it under autocast.
+    ``fmap1``, ``fmap2`` [B, N, C, H, W] float16 give B N edges; an edge's
+    pyramid -- level 0 [H, W, H, W] = fmap1 / 4 . fmap2 / 4 over the channels,
+    level i + 1 the 2 x 2 average of level i as stored -- lives in one slot of
+    a store, one device allocation of ``capacity`` slots (default: the edges
+    given; size it once with e.g. ``max_factors`` plus a batch of new edges).
+
+    ``block(coords)``, ``coords`` [B, N, H, W, 2]: float16 [B, N, num_levels
+    (2r+1)^2, H, W] from one launch.  ``block.append(fmap1, fmap2)`` builds new
+    edges straight into free slots (the store doubles when full);
+    ``block.cat(other)`` copies ``other``'s edges into free slots and returns
+    self; ``block[index]`` keeps the indexed edges by editing the slot table
+    alone -- no volume moves -- and returns self.  ``corr_pyramid`` gathers the
+    reference's list of [B N, H, W, H >> i, W >> i] tensors in edge order.
+
+    Inference only: float32 maps, or an input that requires grad under grad
+    mode, raise ``NotImplementedError``; training keeps the reference's torch
+    composition over ``droid_backends.corr_index_forward`` / ``_backward``."""
+
+    def __init__(self, fmap1, fmap2, num_levels=4, radius=3, capacity=None):
+        self.num_levels = int(num_levels)
+        self.radius = int(radius)
+        if not 1 <= self.num_levels <= CORR_MAX_LEVELS:
+            raise RuntimeError(f"num_levels must lie in [1, {CORR_MAX_LEVELS}]")
+        edges, self.channels, self.ht, self.wd, dev = self._check_maps(fmap1, fmap2, first=True)
+        self._offsets, self.slot_elems = corr_slot_layout(self.ht, self.wd, self.num_levels)
+        self._table = SlotTable(max(edges, 1) if capacity is None else capacity)
+        self._store = torch.empty(self._table.capacity * self.slot_elems, dtype=torch.float16, device=dev)
+        self._slots_dev = None  # the device copy of the table, made when next needed
+        self.append(fmap1, fmap2)
+
+    def _check_maps(self, fmap1, fmap2, first=False):
+        if fmap1.dim() != 5 or fmap1.shape != fmap2.shape:
+            raise RuntimeError("fmap1 and fmap2 must have the same dimensions (B, N, C, H, W)")
+        B, N, C, H, W = fmap1.shape
+        if not first and (C, H, W) != (self.channels, self.ht, self.wd):
+            raise RuntimeError(f"the maps must be (C, H, W) = ({self.channels}, {self.ht}, {self.wd}) like the "
+                               f"block's, got ({C}, {H}, {W})")
+        small = 1 << (self.num_levels - 1)
+        if H < small or W < small:
+            raise RuntimeError(f"H and W must each be at least {small} for {self.num_levels} levels, got {H} x {W}")
+        if C % 32 != 0 or C == 0:
+            raise RuntimeError(f"the channel count {C} must be a positive multiple of 32")
+        for t in (fmap1, fmap2):
+            if t.dtype != torch.float16:
+                raise NotImplementedError(f"CorrBlock: only float16 maps are built (the tracker's autocast), got "
+                                          f"{t.dtype}")
+        if torch.is_grad_enabled() and (fmap1.requires_grad or fmap2.requires_grad):
+            raise NotImplementedError("CorrBlock is inference only: an input requires grad (training keeps the torch "
+                                      "composition)")
+        dev = droid_backends._device_of(fmap1=fmap1, fmap2=fmap2)
+        return B * N, C, H, W, dev
+
+    # -- the store -----------------------------------------------------------
+    def __len__(self):
+        return len(self._table)
+
+    @property
+    def capacity(self):
+        return self._table.capacity
+
+    def _take(self, n):
+        """Slots for n new edges; the store grows first if it is full (the
+        held slots keep their numbers)."""
+        new = self._table.take(n)
+        if self._table.capacity * self.slot_elems != self._store.numel():
+            store = torch.empty(self._table.capacity * self.slot_elems, dtype=torch.float16,
+                                device=self._store.device)
+            store[:self._store.numel()].copy_(self._store)
+            self._store = store
+        self._slots_dev = None
+        return new
+
+    def _slots(self):
+        if self._slots_dev is None:
+            self._slots_dev = torch.tensor(self._table.slots, dtype=torch.int32, device=self._store.device)
+        return self._slots_dev
+
+    @torch.no_grad()
+    def append(self, fmap1, fmap2):
+        """Build the edges of ``fmap1``, ``fmap2`` [B, N, C, H, W] into free
+        slots, after the edges already held.  Returns self."""
+        edges, C, H, W, dev = self._check_maps(fmap1, fmap2)
+        if dev != self._store.device:
+            raise RuntimeError(f"fmap1: expected a tensor on {self._store.device}, got {dev}")
+        if edges:
+            f1 = fmap1.detach().reshape(edges, C, H, W).contiguous()
+            f2 = fmap2.detach().reshape(edges, C, H, W).contiguous()
+            slots = torch.tensor(self._take(edges), dtype=torch.int32, device=dev)
+            corr_build(f1, f2, self._store, slots, self.num_levels)
+        return self
+
+    @torch.no_grad()
+    def cat(self, other):
+        if (other.num_levels, other.ht, other.wd) != (self.num_levels, self.ht, self.wd):
+            raise RuntimeError("cat: the other block has another shape or number of levels")
+        if other._store.device != self._store.device:
+            raise RuntimeError("cat: the other block lives on another device")
+        theirs = list(other._table.slots)
+        if theirs:
+            mine = self._take(len(theirs))
+            dst = self._store.view(-1, self.slot_elems)
+            src = other._store.view(-1, self.slot_elems)
+            for d, s in zip(mine, theirs):
+                dst[d].copy_(src[s])
+        return self
+
+    def __getitem__(self, index):
+        self._table.select(index)
+        self._slots_dev = None
+        return self
+
+    @property
+    def corr_pyramid(self):
+        slots = self._slots().long()
+        rows = self._store.view(-1, self.slot_elems)
+        H, W = self.ht, self.wd
+        return [rows[:, off:off + H * W * (H >> i) * (W >> i)].index_select(0, slots).view(-1, H, W, H >> i, W >> i)
+                for i, off in enumerate(self._offsets)]
+
+    @torch.no_grad()
+    def __call__(self, coords):
+        if coords.dim() != 5 or coords.size(-1) != 2 or coords.dtype != torch.float32:
+            raise RuntimeError("coords must be a float32 tensor of dimensions (B, N, H, W, 2)")
+        B, N, H, W, _ = coords.shape
+        if (H, W) != (self.ht, self.wd) or B * N != len(self._table):
+            raise RuntimeError(f"coords must be (B, N, {self.ht}, {self.wd}, 2) with B N = {len(self._table)} edges, "
+                               f"got {tuple(coords.shape)}")
+        droid_backends._device_of(coords=coords)
+        out = corr_lookup(self._store, self._slots(), coords.reshape(B * N, H, W, 2).contiguous(), self.num_levels,
+                          self.radius)
+        return out.view(B, N, -1, H, W)

@@ -34,7 +34,7 @@ from test_gpu_raster import _cpu_expect, _synthetic, check_against, run_c
 
 pytestmark = pytest.mark.gpu
 
-K_BDS_CAP = 5120  # kBdsCap (raster_fwd.hip): entries k_bin_depth_sort sorts in LDS
+K_BDS_CAP = 5120  # kBdsCap (raster_bin_sort.hip): entries k_bin_depth_sort sorts in LDS
 
 # (W, H, P, SH degree, every opacity or None for the scene's own)
 SHAPES = {

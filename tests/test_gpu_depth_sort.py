@@ -4,7 +4,7 @@
   launch_depth_sort, DepthKeyPlan in csrc/wgsr_common.h; WGSR_DEPTH_SORT=
   global) against the four 8-bit passes over the whole 32-bit keys
   (WGSR_DEPTH_SORT=full): identical depth order and outputs;
-* the default, per-bin depth sort after the bin sort (csrc/raster_fwd.hip
+* the default, per-bin depth sort after the bin sort (csrc/raster_bin_sort.hip
   k_bin_depth_sort: pairs duplicated in index order, every sort bin ordered by
   depth key, ties by index), which has no Gaussian-level order: every raster
   output bit-identical to the global schedules, incl. bins larger than one

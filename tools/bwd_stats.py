@@ -1,6 +1,6 @@
 """Diagnostic: per-entry quadrant histogram of the quad render backward
-(build: VFLAGS="-DWGSR_BWD_STATS=1 -DWGSR_BWD_PAIR=0" tools/build_variant.sh
-stats /tmp/empty; run with WGSR_LIB=.../lib/variants/stats.so).
+(build: VFLAGS="-DWGSR_BWD_STATS=1" tools/build_variant.sh stats /tmp/empty;
+run with WGSR_LIB=.../lib/variants/stats.so).
 
 For every entry the walk evaluates: the set of 8x8 quadrants its ellipse
 reaches (phase 1 runs there) and the set where some pixel took it (phase 2

@@ -1,6 +1,8 @@
 #!/bin/bash
 # Run parity tests + bench for several settings of an environment knob.
-# usage: KNOBS="WGSR_FWD_PPL WGSR_BWD_PPL" VALUES="1 2 4" bash tools/sweep_env.sh
+# Every knob in KNOBS is set to the same value, one run per value.
+# usage: KNOBS="WGSR_BIN_SHIFT" VALUES="1 2" bash tools/sweep_env.sh
+#        KNOBS="WGSR_FWD_DEC" VALUES="0 1" bash tools/sweep_env.sh
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp

@@ -19,6 +19,7 @@
 
 #include <vector>
 
+#include "raster_sh.h"
 #include "wgsr_common.h"
 #include "wgsr_internal.h"
 
@@ -64,14 +65,6 @@ __device__ unsigned long long g_bwd_wgt[3 * kWgtMax];
 // below this many tiles the backward runs k_render_bwd_seg (four waves per
 // tile) instead of k_render_bwd_quad (one); WGSR_BWD_SPLIT_BELOW overrides
 constexpr int kBwdSplitBelowTiles = 3072;
-
-constexpr float SH_C0 = 0.28209479177387814f;
-constexpr float SH_C1 = 0.4886025119029199f;
-__constant__ float SH_C2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f,
-                               -1.0925484305920792f, 0.5462742152960396f};
-__constant__ float SH_C3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f,
-                               0.3731763325901154f,  -0.4570457994644658f, 1.445305721320277f,
-                               -0.5900435899266435f};
 
 // The render backward sums, over a tile's pixels, u = G dL/dalpha (dx, dy),
 // its moments u_x dx, u_x dy, u_y dy and G dL/dalpha; the entry's own
@@ -1046,13 +1039,9 @@ constexpr int kGbWave = 64;
 constexpr int kGbcThreads = 256;
 constexpr int kRecChunk = 512;  // flattened record slots staged in LDS at a time
 // ... with 256 / 512 Gaussians per workgroup, whose smaller lists leave room
-// for 768 slots at four workgroups per CU: fewer chunk round trips
-#ifndef WGSR_GBC_IDX
-#define WGSR_GBC_IDX 1
-#endif
-#ifndef WGSR_GBC_CHUNK_SMALL
-#define WGSR_GBC_CHUNK_SMALL 768
-#endif
+// for 768 slots at four workgroups per CU: fewer chunk round trips (200k:
+// 58.3 -> 57.0 us; 1024 slots leave three workgroups per CU, 65.5 us)
+constexpr int kRecChunkSmall = 768;
 template <int kR>
 __global__ __launch_bounds__(kGbcThreads) void k_gauss_bwd_compact(
     int P, int D, int M, const uint8_t* __restrict__ gflag, const uint32_t* __restrict__ slot_start,
@@ -1065,7 +1054,7 @@ __global__ __launch_bounds__(kGbcThreads) void k_gauss_bwd_compact(
     float* __restrict__ o_cov, float* __restrict__ o_sh, float* __restrict__ o_sc, float* __restrict__ o_rot,
     float* __restrict__ o_tau) {
   constexpr int NW = kGbcThreads / 64;
-  constexpr int kRecChunk = kR == 4 ? wgsr::kRecChunk : WGSR_GBC_CHUNK_SMALL;
+  constexpr int kRecChunk = kR == 4 ? wgsr::kRecChunk : kRecChunkSmall;
   __shared__ uint32_t s_list[(kGbcThreads * kR)];
   __shared__ uint32_t s_s0[(kGbcThreads * kR)], s_n[(kGbcThreads * kR)], s_off[(kGbcThreads * kR) + 1];
   __shared__ uint2 s_tmp4[4];
@@ -1088,8 +1077,9 @@ __global__ __launch_bounds__(kGbcThreads) void k_gauss_bwd_compact(
   // record slots in index order (ImageLayout::meta[2], the default sort-bin
   // forward): each row's slot range from two coalesced slot_start words,
   // loaded with the flags -- no dependent gather of the live rows' ranges
-  // (the last row's end from its list length)
-  const bool idx = WGSR_GBC_IDX && meta[2] != 0u;  // (uniform)
+  // (the last row's end from its list length; 1M: 55.6 -> 54.5 us).  The
+  // depth-ordered fallback forward keeps the gather.
+  const bool idx = meta[2] != 0u;  // (uniform)
   uint32_t ss[kR], se[kR];
   if (idx) {
 #pragma unroll

@@ -11,7 +11,6 @@
 namespace wgsr {
 
 constexpr int kTile = 16;             // tile edge in pixels (SURVEY A.1 BLOCK_X/Y)
-constexpr int kTilePix = kTile * kTile;
 constexpr int kWave = 64;
 constexpr float kNearZ = 0.2f;        // near-plane cull
 constexpr float kMinAlpha = 1.0f / 255.0f;
@@ -78,18 +77,10 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
   return v;
 }
 
-// Sum of x over each 16-lane row; lane 15 of every row ends with the row sum.
-// Quad butterfly (quad_perm [1,0,3,2], [2,3,0,1]) then row_shr:4 and
-// row_shr:8 with bound_ctrl (shifted-in lanes read 0): VALU-only DPP adds.
-__device__ __forceinline__ float dpp_row_sum16(float x) {
-  x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xf, 0xf, true));
-  x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x4E, 0xf, 0xf, true));
-  x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x114, 0xf, 0xf, true));
-  x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x118, 0xf, 0xf, true));
-  return x;
-}
-
-// The same for unsigned sums / maxima (bound_ctrl zeros: the identity of both)
+// Sum / maximum of x over each 16-lane row; lane 15 of every row ends with
+// the row's result.  Quad butterfly (quad_perm [1,0,3,2], [2,3,0,1]) then
+// row_shr:4 and row_shr:8 with bound_ctrl (shifted-in lanes read 0, the
+// identity of both): VALU-only DPP operations.
 __device__ __forceinline__ uint32_t dpp_row_sum16_u32(uint32_t x) {
   x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xf, 0xf, true);
   x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x4E, 0xf, 0xf, true);
@@ -115,11 +106,6 @@ __device__ __forceinline__ uint32_t wave_maximum_u32(uint32_t x) {
   x = dpp_row_max16_u32(x);
   return max(max((uint32_t)__builtin_amdgcn_readlane((int)x, 15), (uint32_t)__builtin_amdgcn_readlane((int)x, 31)),
              max((uint32_t)__builtin_amdgcn_readlane((int)x, 47), (uint32_t)__builtin_amdgcn_readlane((int)x, 63)));
-}
-
-__device__ __forceinline__ float2 permlane32_swap_add(float a, float b) {
-  auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  return make_float2(__uint_as_float(r[0]), __uint_as_float(r[1]));
 }
 
 // Wave-wide sums of 10 per-lane values, stored to dst[0..9] by 4 lanes.
@@ -377,14 +363,6 @@ __device__ __forceinline__ bool ellipse_hits(const float4& A, const float4& B, i
   return fminf(fminf(e0, e1), fminf(e2, e3)) <= lim * 1.001f + 1e-2f;
 }
 
-template <int PPL>
-__device__ __forceinline__ bool all_done(const bool (&d)[PPL]) {
-  bool r = true;
-#pragma unroll
-  for (int p = 0; p < PPL; ++p) r = r && d[p];
-  return r;
-}
-
 // ---- per-wave SH slabs: rows of S = 3M floats for 64 consecutive Gaussians
 // are contiguous in HBM; they move between HBM and LDS rows padded to S + 1
 // floats (a lane walking its own row is then bank-conflict free).  All loads
@@ -626,8 +604,6 @@ __device__ __forceinline__ f3 cross3(f3 a, f3 b) {
 
 // The caller's matrices are the row-vector (transposed) forms, read as
 // column-major 4x4: m[4*c + r] = M[r][c] of the column-vector matrix.
-struct Mat16 { float m[16]; };
-
 __device__ __forceinline__ f3 xform43(const float* m, f3 p) {
 #pragma clang fp contract(off)
   return {m[0] * p.x + m[4] * p.y + m[8] * p.z + m[12], m[1] * p.x + m[5] * p.y + m[9] * p.z + m[13],
@@ -737,15 +713,11 @@ __host__ __device__ constexpr size_t align256(size_t x) { return (x + 255) & ~si
 // kSmallSortItems so that a 1M-key pass still spreads over ~1000 workgroups
 // (4096-key tiles would leave a 1M-key pass at 245, under one per CU; 2048-key
 // tiles measured faster than 1024).
-#ifndef WGSR_SMALL_SORT_ITEMS
-#define WGSR_SMALL_SORT_ITEMS 8
-#endif
+constexpr int kSmallSortItems = 8;
 // and sorts of up to kTinySortN keys (TUM-scale frames) kTinySortItems: a
 // pass over 100k keys is a single round of workgroups, whose time is one
 // workgroup's latency (1024-key tiles: depth sort 52 -> 42 us at 100k)
-#ifndef WGSR_TINY_SORT_ITEMS
-#define WGSR_TINY_SORT_ITEMS 4
-#endif
+constexpr int kTinySortItems = 4;
 // (the tile is 256 x kSortItems keys whatever the workgroup size: 2048-key
 // tiles lost for the 2.4 M bin pairs, scatter 39.7 vs 35.7 us, round 5)
 constexpr int kSortItems = 16;
@@ -757,8 +729,6 @@ constexpr int kSortItems = 16;
 // workgroups per CU, 512 slots for the 587 tiles).  Sorts with smaller tiles
 // keep 256 threads (not measured).
 constexpr int kWideSortThreads = 512;
-constexpr int kSmallSortItems = WGSR_SMALL_SORT_ITEMS;
-constexpr int kTinySortItems = WGSR_TINY_SORT_ITEMS;
 constexpr size_t kSmallSortN = size_t(1) << 21;
 constexpr size_t kTinySortN = size_t(1) << 18;
 constexpr int kScanTile = 1024;                      // elements per scan workgroup

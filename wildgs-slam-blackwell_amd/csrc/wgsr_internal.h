@@ -62,7 +62,7 @@ int num_bits(uint32_t n);  // bits needed to represent values in [0, n)
 // thread-local error message plumbing for the C ABI
 int set_error(int code, const char* fmt, ...);
 
-// forward stages (raster_fwd.hip)
+// ---- preprocess (raster_pre.hip) --------------------------------------------
 // rect_pairs[0..kRectPairLanes) += upstream's num_rendered contributions (rect
 // areas); rect_pairs[kRectPairLanes..2 kRectPairLanes) += exact list lengths
 // rect_pairs[2 kRectPairLanes..3 kRectPairLanes) += bins touched (bshift > 0;
@@ -73,6 +73,10 @@ hipError_t launch_preprocess(const wgsr_raster_args& a, void* geom, int32_t* rad
 // overflow, clamped N_bin] and the overflow flag into meta[1]
 hipError_t launch_cap_counts(const unsigned long long* partial, uint64_t cap_rect, uint64_t cap_bin, uint32_t* counts,
                              uint32_t* meta, hipStream_t s);
+// present[i] = Gaussian i lies beyond the near plane of `view` (wgsr_mark_visible)
+hipError_t launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t s);
+
+// ---- tile lists (raster_lists.hip) ------------------------------------------
 // Sort bins: after packed_scan_blocks, the scan's down-sweep (slot_start[g],
 // the slot flags zeroed) fused with the (bin | exact tile mask << 16,
 // Gaussian) pair expansion.  Sets ImageLayout::meta[2] when the slots follow
@@ -84,6 +88,29 @@ hipError_t launch_duplicate_bins(const wgsr_raster_args& a, void* geom, const ui
                                  uint32_t cap_pairs = 0xFFFFFFFFu);
 hipError_t launch_duplicate(const wgsr_raster_args& a, const void* geom, const uint32_t* sorted_g, uint32_t P,
                             uint32_t* keys, uint32_t* slot_g, uint8_t* pflag, hipStream_t s);
+// every bin's [start, end) in the NB bin-sorted keys, unless a one-pass sort
+// already wrote them (bounds_done); shared by launch_expand_bins and
+// launch_bin_depth_sort
+hipError_t make_bin_bounds(const uint32_t* sorted_keys, uint32_t NB, int nbins, uint2* bounds, bool bounds_done,
+                           hipStream_t s);
+// per-tile exact lists out of the bin-sorted pairs: ranges / tile_len per
+// tile, the lists in bin-sized regions of `lists` (2^2s x NB entries)
+hipError_t launch_expand_bins(const wgsr_raster_args& a, const uint32_t* sorted_keys, const uint32_t* sorted_g,
+                              uint32_t NB, int bshift, uint2* bounds, bool bounds_done, uint32_t* lists, uint2* ranges,
+                              uint32_t* tile_len, uint32_t* meta, hipStream_t s);
+// tile ranges of the exact (Gaussian, tile) pair sort
+hipError_t launch_ranges(const uint32_t* sorted_keys, uint32_t N, int ntiles, uint2* ranges, uint32_t* len,
+                         uint32_t* meta, hipStream_t s);
+// the render backward's launch order (tiles by deepest contributor, per XCD
+// chunk): the forward writes it, so its kernel lives with the lists
+hipError_t launch_tile_order(const uint32_t* work_quads, int ntiles, uint32_t* order, hipStream_t s);
+// p[0..n) = 0 by a kernel (graph-capturable without a memset node)
+hipError_t launch_zero_u32(uint32_t* p, size_t n, hipStream_t s);
+// wgsr_check_tile_lists' kernel (lists region sizes from num_rendered and the bin shift)
+hipError_t launch_check_tile_lists(const wgsr_raster_args& a, int bshift, uint64_t num_rendered, const void* binning,
+                                   const void* image, uint32_t* bad, hipStream_t s);
+
+// ---- per-bin depth sort (raster_bin_sort.hip) -------------------------------
 // stable argsort of n <= argsort_small_max() keys in one workgroup (perm: positions)
 uint32_t argsort_small_max();
 hipError_t launch_argsort_small(const uint32_t* keys, uint32_t n, uint32_t* perm, hipStream_t s);
@@ -97,28 +124,15 @@ hipError_t launch_bin_depth_sort(const wgsr_raster_args& a, const uint32_t* sort
                                  uint32_t NB, int bshift, uint2* bounds, bool bounds_done, const uint32_t* gdepth,
                                  void* scratch, uint32_t* lists, uint2* ranges, uint32_t* tile_len, uint32_t* meta,
                                  hipStream_t s);
-// per-tile exact lists out of the bin-sorted pairs: ranges / tile_len per
-// tile, the lists in bin-sized regions of `lists` (2^2s x NB entries)
-hipError_t launch_expand_bins(const wgsr_raster_args& a, const uint32_t* sorted_keys, const uint32_t* sorted_g,
-                              uint32_t NB, int bshift, uint2* bounds, bool bounds_done, uint32_t* lists, uint2* ranges,
-                              uint32_t* tile_len, uint32_t* meta, hipStream_t s);
-// tile ranges of the exact (Gaussian, tile) pair sort
-hipError_t launch_ranges(const uint32_t* sorted_keys, uint32_t N, int ntiles, uint2* ranges, uint32_t* len,
-                         uint32_t* meta, hipStream_t s);
-// the backward's launch order (tiles by deepest contributor, per XCD chunk)
-hipError_t launch_tile_order(const uint32_t* work_quads, int ntiles, uint32_t* order, hipStream_t s);
+
+// ---- render forward (raster_render_fwd.hip) ---------------------------------
+// k_render_fwd_dec, or k_render_fwd1 with WGSR_FWD_DEC=0
 hipError_t launch_render_fwd(const wgsr_raster_args& a, const uint2* ranges, const uint32_t* point_g,
                              const void* geom, float* out_color, float* out_depth,
                              float* out_opacity, float* final_T, uint32_t* n_contrib, int32_t* n_touched,
                              uint32_t* tile_m4, hipStream_t s);
-// p[0..n) = 0 by a kernel (graph-capturable without a memset node)
-hipError_t launch_zero_u32(uint32_t* p, size_t n, hipStream_t s);
-// wgsr_check_tile_lists' kernel (lists region sizes from num_rendered and the bin shift)
-hipError_t launch_check_tile_lists(const wgsr_raster_args& a, int bshift, uint64_t num_rendered, const void* binning,
-                                   const void* image, uint32_t* bad, hipStream_t s);
-hipError_t launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t s);
 
-// backward stages (raster_bwd.hip)
+// ---- backward stages (raster_bwd.hip) ---------------------------------------
 // the tile lists: lists_bins when the forward's ImageLayout::meta word says so, else lists_exact
 hipError_t launch_render_bwd(const wgsr_raster_args& a, const uint2* ranges, const uint32_t* order,
                              const uint32_t* meta, const uint32_t* lists_exact, const uint32_t* lists_bins,

@@ -989,6 +989,36 @@ int wgsr_droid_reproject(const float* poses, const float* disps, const float* in
                          int num, int ht, int wd, const int64_t* ii, const int64_t* jj, int n, int flags,
                          float* coords, float* valid, float* Ji, float* Jj, float* Jz, void* stream);
 
+/* ---- Convex upsampling of the tracker's disparities (cvx_upsample,
+ * droid_net.py:23-37; DepthVideo.upsample, depth_video.py:179-183;
+ * csrc/droid_upsample.hip; wgsr.frontend.upsample).  With pad the zero-padded
+ * coarse map,
+ *   up[i, 8y+a, 8x+b, c] = sum_{k=0..8} softmax_k(mask[i, 64k + 8a + b, y, x])
+ *                                       * pad[i, y + k/3 - 1, x + k%3 - 1, c]:
+ * the softmax in fp32 with the maximum subtracted, the weights never rounded.
+ * One launch, no allocation, no synchronisation, no host read.
+ * src_index [n] (int64, or null: entry i reads frame i) names the frame of
+ * `data` / `disps` [n_src, ht, wd, dim] entry i reads; out_index [n] (or null)
+ * the frame of `out` [n_out, 8 ht, 8 wd, dim] it writes: every element of an
+ * addressed frame is written, other frames are untouched; the entries of
+ * out_index must be distinct.  out must be 16-byte aligned.
+ * status (one device word, written by every call): 0, or WGSR_UPSAMPLE_BAD_*
+ * when an index lies outside its range -- the call then writes nothing else. */
+#define WGSR_UPSAMPLE_BAD_SRC 1u /* a src_index outside [0, n_src) */
+#define WGSR_UPSAMPLE_BAD_OUT 2u /* an out_index outside [0, n_out) */
+/* mask [n, 576, ht, wd] of mask_dtype (WGSR_DTYPE_F32 or _F16); 1 <= dim <= 4. */
+int wgsr_droid_cvx_upsample(const float* data, const int64_t* src_index, const void* mask, int mask_dtype,
+                            float* out, const int64_t* out_index, int n, int n_src, int n_out, int ht, int wd,
+                            int dim, uint32_t* status, void* stream);
+/* The same on dim = 1 with the mask head (GraphAgg.upmask, droid_net.py:61-63:
+ * a 1 x 1 convolution) computed inside the launch: feat [n, C, ht, wd] fp16
+ * (C a multiple of 32, 16-byte aligned), weight [576, C] fp16 (16-byte
+ * aligned), bias [576] fp32.  logit = fp16(fp32 MFMA sum over C + bias): the
+ * value the convolution hands on under autocast.  No logit reaches memory. */
+int wgsr_droid_upmask_upsample(const void* feat, const void* weight, const float* bias, int C, const float* disps,
+                               const int64_t* src_index, float* out, const int64_t* out_index, int n, int n_src,
+                               int n_out, int ht, int wd, uint32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

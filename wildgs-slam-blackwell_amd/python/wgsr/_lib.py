@@ -338,6 +338,11 @@ def load():
         L.wgsr_lie_se3.argtypes = [c_int, _fp, c_i64, _fp, c_i64, _fp, c_i64, _fp]
         L.wgsr_droid_reproject.restype = c_int
         L.wgsr_droid_reproject.argtypes = [_fp] * 3 + [c_int] * 4 + [_fp, _fp, c_int, c_int] + [_fp] * 5 + [_fp]
+        # wgsr.frontend.upsample (csrc/droid_upsample.hip)
+        L.wgsr_droid_cvx_upsample.restype = c_int
+        L.wgsr_droid_cvx_upsample.argtypes = [_fp, _fp, _fp, c_int, _fp, _fp] + [c_int] * 6 + [_fp, _fp]
+        L.wgsr_droid_upmask_upsample.restype = c_int
+        L.wgsr_droid_upmask_upsample.argtypes = [_fp, _fp, _fp, c_int, _fp, _fp, _fp, _fp] + [c_int] * 5 + [_fp, _fp]
         L.wgsr_last_error.restype = ctypes.c_char_p
         L.wgsr_last_error.argtypes = []
         L.wgsr_version.restype = ctypes.c_char_p
@@ -384,6 +389,7 @@ EXPORTED_SYMBOLS = (
     "wgsr_droid_corr_slot_bytes", "wgsr_droid_corr_build", "wgsr_droid_corr_lookup",
     "wgsr_droid_ba_workspace_bytes", "wgsr_droid_ba", "wgsr_droid_ba_system", "wgsr_droid_ba_stage_events",
     "wgsr_lie_se3", "wgsr_droid_reproject",
+    "wgsr_droid_cvx_upsample", "wgsr_droid_upmask_upsample",
 )
 
 VIEW_RECORD_FLOATS = 12   # WGSR_VIEW_RECORD_FLOATS

@@ -18,6 +18,12 @@
 * ``reproject``         DepthVideo.reproject / projective_ops.projective_transform
                         (projective_ops.py:110-139), one fused launch
                         (csrc/lie.hip) instead of the composition of group ops
+* ``upsample``          DepthVideo.upsample (depth_video.py:179-183): the convex
+                        upsampling of the disparities in place on the video
+                        buffers, one launch (csrc/droid_upsample.hip), with
+                        ``cvx_upsample`` / ``upsample_disp`` (droid_net.py:23-45)
+                        and ``upsample_from_features``, which computes the mask
+                        head (GraphAgg.upmask) inside the same launch
 
 poses [num, 7] = (tx, ty, tz, qx, qy, qz, qw), world to camera; disps
 [num, ht, wd]; intrinsics [4] = (fx, fy, cx, cy); device fp32 tensors.
@@ -25,6 +31,7 @@ poses [num, 7] = (tx, ty, tz, qx, qy, qz, qw), world to camera; disps
 from __future__ import annotations
 
 import heapq
+import weakref
 
 import torch
 import torch.nn.functional as F
@@ -505,3 +512,191 @@ class CorrBlock:
         out = corr_lookup(self._store, self._slots(), coords.reshape(B * N, H, W, 2).contiguous(), self.num_levels,
                           self.radius)
         return out.view(B, N, -1, H, W)
+
+
+# ---------------------------------------------------------------------------
+# Convex upsampling (csrc/droid_upsample.hip)
+# ---------------------------------------------------------------------------
+UPSAMPLE_MASK_CHANNELS = 576  # 9 neighbours x 8 x 8 sub-positions
+UPSAMPLE_MAX_DIM = 4          # kUpMaxDim
+UPSAMPLE_STATUS = {1: "an index is outside the source frames (WGSR_UPSAMPLE_BAD_SRC)",
+                   2: "an index is outside the output frames (WGSR_UPSAMPLE_BAD_OUT)"}
+
+
+def _inference_only(who, **tensors):
+    if torch.is_grad_enabled():
+        for name, t in tensors.items():
+            if t is not None and t.requires_grad:
+                raise NotImplementedError(f"{who} is inference only: {name} requires grad (training keeps the torch "
+                                          "composition)")
+
+
+def _upsample_mask(mask, n, ht, wd):
+    if mask.dtype not in droid_backends._DTYPE_TAG:
+        raise NotImplementedError(f"mask must be float16 or float32, got {mask.dtype}")
+    if mask.numel() != n * UPSAMPLE_MASK_CHANNELS * ht * wd:
+        raise ValueError(f"mask must hold {UPSAMPLE_MASK_CHANNELS} channels for each of the {n} maps of {ht} x {wd}: "
+                         f"got {tuple(mask.shape)}")
+    droid_backends._contiguous(mask=mask)
+    return mask
+
+
+def _upsample_index(ix, dev):
+    ix = torch.as_tensor(ix)
+    if ix.device.type == "cuda" and ix.device != dev:
+        raise RuntimeError(f"ix: expected a tensor on {dev}, got {ix.device}")
+    return ix.to(dev, torch.int64).reshape(-1).contiguous()
+
+
+def _upsample_buffers(disps, disps_up):
+    droid_backends._contiguous(disps=disps, disps_up=disps_up)
+    dev = droid_backends._device_of(disps=disps, disps_up=disps_up)
+    if disps.dim() != 3 or disps_up.dim() != 3 or disps.dtype != torch.float32 or disps_up.dtype != torch.float32:
+        raise RuntimeError("disps and disps_up must be float32 tensors of dimensions (num, ht, wd) and (num, 8 ht, 8 wd)")
+    ht, wd = disps.size(1), disps.size(2)
+    if tuple(disps_up.shape[1:]) != (8 * ht, 8 * wd):
+        raise ValueError(f"disps_up must be (num, {8 * ht}, {8 * wd}) for disps of {ht} x {wd}: got "
+                         f"{tuple(disps_up.shape)}")
+    return dev, ht, wd
+
+
+def _upsample_raise(who, status):
+    word = int(status.item())
+    if word:
+        what = "; ".join(msg for bit, msg in UPSAMPLE_STATUS.items() if word & bit)
+        raise RuntimeError(f"{who}: {what} (status {word}); nothing was written")
+
+
+def _cvx_launch(who, data, src_index, mask, out, out_index, n, dim, check, dev):
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    L = _lib.load()
+    with torch.cuda.device(dev):
+        _lib.check(L.wgsr_droid_cvx_upsample(data.data_ptr(), _lib.ptr(src_index), mask.data_ptr(),
+                                             droid_backends._DTYPE_TAG[mask.dtype], out.data_ptr(),
+                                             _lib.ptr(out_index), n, data.size(0), out.size(0), data.size(1),
+                                             data.size(2), dim, status.data_ptr(), _lib.stream_handle(dev)))
+    if check:
+        _upsample_raise(who, status)
+
+
+def cvx_upsample(data, mask):
+    """The reference's ``cvx_upsample`` (droid_net.py:23-37): ``data`` [n, ht,
+    wd, dim] float32 (dim <= 4), ``mask`` n x 576 x ht x wd values (float16 or
+    float32, any shape that views to it) -> [n, 8 ht, 8 wd, dim] float32: each
+    fine pixel the softmax-weighted sum of the 3 x 3 coarse neighbourhood
+    (zero-padded), the softmax in fp32, one launch."""
+    _inference_only("cvx_upsample", data=data, mask=mask)
+    dev = droid_backends._device_of(data=data, mask=mask)
+    if data.dim() != 4 or data.dtype != torch.float32:
+        raise RuntimeError("data must be a float32 tensor of dimensions (n, ht, wd, dim)")
+    n, ht, wd, dim = data.shape
+    if not 1 <= dim <= UPSAMPLE_MAX_DIM:
+        raise NotImplementedError(f"data: dim = {dim} outside [1, {UPSAMPLE_MAX_DIM}] is not built")
+    mask = _upsample_mask(mask.detach(), n, ht, wd)
+    data = data.detach().contiguous()
+    out = torch.empty(n, 8 * ht, 8 * wd, dim, dtype=torch.float32, device=dev)
+    if out.numel():
+        _cvx_launch("cvx_upsample", data, None, mask, out, None, n, dim, False, dev)
+    return out
+
+
+def upsample_disp(disp, mask):
+    """The reference's ``upsample_disp`` (droid_net.py:40-45): ``disp`` [batch,
+    num, ht, wd] -> [batch, num, 8 ht, 8 wd]."""
+    if disp.dim() != 4:
+        raise RuntimeError("disp must have dimensions (batch, num, ht, wd)")
+    batch, num, ht, wd = disp.shape
+    return cvx_upsample(disp.reshape(batch * num, ht, wd, 1), mask).view(batch, num, 8 * ht, 8 * wd)
+
+
+def upsample(disps, disps_up, ix, mask, check=True):
+    """DepthVideo.upsample on the video buffers: ``disps_up[ix] =
+    cvx_upsample(disps[ix][..., None], mask)`` in one launch that reads the
+    frames ``ix`` of ``disps`` [num, ht, wd] and writes the frames ``ix`` of
+    ``disps_up`` [num, 8 ht, 8 wd] in place; no gathered copy, no scatter, the
+    other frames untouched.  ``ix`` [n] int64 with distinct entries in any order
+    (n = 1 included); ``mask`` the n x 576 x ht x wd outputs of the mask head,
+    float16 or float32.  The kernel validates ``ix`` on the device; ``check``
+    reads the status word back and raises ``RuntimeError`` for an index outside
+    the buffers (``disps_up`` is then unchanged).  ``check=False`` skips that
+    read: no synchronisation, and the call can be captured in a graph (``ix``
+    then has to be a device tensor already)."""
+    _inference_only("upsample", disps=disps, mask=mask)
+    dev, ht, wd = _upsample_buffers(disps, disps_up)
+    droid_backends._device_of(mask=mask)
+    ix = _upsample_index(ix, dev)
+    n = ix.numel()
+    mask = _upsample_mask(mask.detach(), n, ht, wd)
+    if n and disps_up[0].numel():
+        _cvx_launch("upsample", disps.detach().unsqueeze(-1), ix, mask, disps_up.detach().unsqueeze(-1), ix, n, 1,
+                    check, dev)
+
+
+_HEAD_CACHE = {}    # (data_ptr, version, dtype, shape) of a parameter -> its kernel-ready copy
+_HEAD_CACHE_MAX = 8
+
+
+def _head_param(src, dtype, shape):
+    """``src`` as a contiguous ``dtype`` tensor of ``shape``; a converted copy
+    is kept until the parameter is written again (its version changes).  An
+    entry also holds a weak reference to the tensor it was made from and
+    serves that tensor only: the allocator hands a freed tensor's address, with
+    version 0 again, to the next tensor of its size."""
+    t = src.detach()
+    if t.dtype == dtype and t.is_contiguous() and t.data_ptr() % 16 == 0:
+        return t.view(shape)
+    key = (t.data_ptr(), t._version, t.dtype, tuple(t.shape), t.device)
+    hit = _HEAD_CACHE.get(key)
+    if hit is not None and hit[0]() is src:
+        return hit[1]
+    _HEAD_CACHE.pop(key, None)
+    if len(_HEAD_CACHE) >= _HEAD_CACHE_MAX:
+        _HEAD_CACHE.pop(next(iter(_HEAD_CACHE)))
+    copy = t.reshape(shape).to(dtype).contiguous()
+    _HEAD_CACHE[key] = (weakref.ref(src), copy)
+    return copy
+
+
+def upsample_from_features(disps, disps_up, ix, feat, weight, bias, check=True):
+    """``upsample`` with the mask head inside the launch: ``feat`` [n, C, ht,
+    wd] float16 (a leading batch dimension of 1 is accepted; C a multiple of
+    32) is what ``GraphAgg`` feeds to ``self.upmask``, ``weight`` that
+    ``Conv2d``'s [576, C, 1, 1] (or [576, C]) and ``bias`` its [576].  A logit
+    is the fp32 MFMA sum over C plus the bias, rounded once to float16 -- the
+    value the convolution hands on under autocast -- and never reaches memory.
+    float32 parameters are converted once and the copy kept (keyed on the
+    parameter's address and version)."""
+    _inference_only("upsample_from_features", disps=disps, feat=feat, weight=weight, bias=bias)
+    dev, ht, wd = _upsample_buffers(disps, disps_up)
+    droid_backends._device_of(feat=feat, weight=weight, bias=bias)
+    ix = _upsample_index(ix, dev)
+    n = ix.numel()
+    if feat.dtype != torch.float16:
+        raise NotImplementedError(f"feat: only float16 features are built (the tracker's autocast), got {feat.dtype}")
+    if feat.dim() == 5 and feat.size(0) == 1:
+        feat = feat[0]
+    if feat.dim() != 4 or feat.size(0) != n or tuple(feat.shape[2:]) != (ht, wd):
+        raise ValueError(f"feat must be (n, C, ht, wd) = ({n}, C, {ht}, {wd}): got {tuple(feat.shape)}")
+    C = feat.size(1)
+    if C == 0 or C % 32 != 0:
+        raise ValueError(f"feat: the channel count C = {C} must be a positive multiple of 32")
+    if weight.dim() not in (2, 4) or weight.size(0) != UPSAMPLE_MASK_CHANNELS or weight.numel() != \
+            UPSAMPLE_MASK_CHANNELS * C:
+        raise ValueError(f"weight must be ({UPSAMPLE_MASK_CHANNELS}, {C}) or ({UPSAMPLE_MASK_CHANNELS}, {C}, 1, 1): "
+                         f"got {tuple(weight.shape)}")
+    if bias.numel() != UPSAMPLE_MASK_CHANNELS:
+        raise ValueError(f"bias must hold {UPSAMPLE_MASK_CHANNELS} values: got {tuple(bias.shape)}")
+    droid_backends._contiguous(feat=feat)
+    w16 = _head_param(weight, torch.float16, (UPSAMPLE_MASK_CHANNELS, C))
+    b32 = _head_param(bias, torch.float32, (UPSAMPLE_MASK_CHANNELS,))
+    if not n or not disps_up[0].numel():
+        return
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    L = _lib.load()
+    with torch.cuda.device(dev):
+        _lib.check(L.wgsr_droid_upmask_upsample(feat.data_ptr(), w16.data_ptr(), b32.data_ptr(), C, disps.data_ptr(),
+                                                ix.data_ptr(), disps_up.data_ptr(), ix.data_ptr(), n, disps.size(0),
+                                                disps_up.size(0), ht, wd, status.data_ptr(),
+                                                _lib.stream_handle(dev)))
+    if check:
+        _upsample_raise("upsample_from_features", status)

@@ -1019,6 +1019,62 @@ int wgsr_droid_upmask_upsample(const void* feat, const void* weight, const float
                                const int64_t* src_index, float* out, const int64_t* out_index, int n, int n_src,
                                int n_out, int ht, int wd, uint32_t* status, void* stream);
 
+/* ---- The 3 x 3 convolutions after the ConvGRU in the tracker's update
+ * operator (UpdateModule.delta / .weight, droid_net.py:102-115, 141-145;
+ * GraphAgg.forward up to eta and the input of upmask, droid_net.py:65-77;
+ * csrc/droid_conv3x3.hip; wgsr.frontend.update_heads / graph_agg).  One
+ * implicit-GEMM kernel: padding 1, stride 1, C_in = 128, maps [*, 128, ht, wd]
+ * fp16 contiguous (NCHW), fp16 weights, fp32 accumulation by
+ * v_mfma_f32_16x16x32_f16, fp32 bias, the epilogue in fp32.  A value that goes
+ * to memory as an activation is rounded to fp16 exactly once (autocast's
+ * rounding point); the heads' outputs (delta, weight, eta) are written as fp32
+ * and never rounded to fp16, which is more exact than autocast.
+ *
+ * Packed parameters (a host-side layout; wgsr.frontend.pack_conv3x3 builds it,
+ * unpack_conv3x3 inverts it).  For W [C_out, 128, 3, 3] and R = ceil(C_out /
+ * 16) row blocks the packed weights are R x 9 x 4 x 64 x 8 fp16 values:
+ *   packed[(((rb 9 + tap) 4 + ks) 64 + lane) 8 + j]
+ *     = W[16 rb + (lane & 15)][32 ks + 8 (lane >> 4) + j][tap / 3][tap % 3],
+ * zero where the row is >= C_out -- the 16 x 32 MFMA A operand of row block
+ * rb, tap and K-step ks as a wave reads it, 16 contiguous bytes per lane.  The
+ * packed bias is fp32 [16 R], zero past C_out.  Both 16-byte aligned.
+ *
+ * Every call: ht x wd < 2^20, at most 65535 maps; launches only -- no
+ * allocation, no synchronisation, no host read -- and capturable in a HIP
+ * graph.  The LDS a workgroup needs (48976 bytes) is checked against the
+ * device's limit before the first launch: an error return, never a launch. */
+/* out[n, C_out, ht, wd] fp16 = fp16(ReLU(conv(x) + bias)); C_out a multiple of
+ * 128.  Every element of out is written. */
+int wgsr_droid_conv3x3_relu(const void* x, const void* w_packed, const float* b_packed, int c_out, void* out, int n,
+                            int ht, int wd, void* stream);
+/* net [n, 128, ht, wd] fp16.  hidden_w / hidden_b: the packed 256-row stack of
+ * delta.0 (rows 0 .. 127) and weight.0 (rows 128 .. 255), both of which read
+ * net: one launch into the caller's scratch `hidden` [n, 256, ht, wd] fp16.
+ * delta_w / weight_w: the packed second layers (C_out = 2, one 16-row block
+ * each).  delta [n, ht, wd, 2] fp32 = conv(hidden[:, :128]) + bias; weight
+ * [n, ht, wd, 2] fp32 = sigmoid(conv(hidden[:, 128:]) + bias): the permuted
+ * form UpdateModule.forward returns.  Three launches; every element of hidden,
+ * delta and weight is written. */
+int wgsr_droid_update_heads(const void* net, const void* hidden_w, const float* hidden_b, const void* delta_w,
+                            const float* delta_b, const void* weight_w, const float* weight_b, void* hidden,
+                            float* delta, float* weight, int n, int ht, int wd, void* stream);
+/* net [n, 128, ht, wd] fp16, ix [n] int64: the group (source frame, 0 .. G-1)
+ * of each edge.  mean [G, 128, ht, wd] fp16 (the caller's scratch) = the mean
+ * over each group's edges, in ascending edge index, of ReLU(conv1(net) +
+ * bias), summed in fp32 by one lane per element (no atomics: two runs are
+ * bit-identical), x 1 / count, rounded once; a group without an edge gives
+ * zeros (scatter_mean).  feat [G, 128, ht, wd] fp16 = fp16(ReLU(conv2(mean) +
+ * bias)), what wgsr_droid_upmask_upsample takes; eta [G, ht, wd] fp32 = 0.01
+ * softplus(conv_eta(feat) + bias) (softplus(v) = v above 20, as torch).
+ * Three launches, the edge lists read from ix inside the first.
+ * status (one device word, written by every call): 0, or
+ * WGSR_GRAPH_AGG_BAD_IX when an entry of ix lies outside [0, G) -- the call
+ * then writes nothing else (mean, feat and eta are untouched). */
+#define WGSR_GRAPH_AGG_BAD_IX 1u
+int wgsr_droid_graph_agg(const void* net, const int64_t* ix, int n, int G, const void* conv1_w, const float* conv1_b,
+                         const void* conv2_w, const float* conv2_b, const void* eta_w, const float* eta_b,
+                         void* mean, void* feat, float* eta, int ht, int wd, uint32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

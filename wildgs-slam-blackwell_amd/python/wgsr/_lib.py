@@ -343,6 +343,13 @@ def load():
         L.wgsr_droid_cvx_upsample.argtypes = [_fp, _fp, _fp, c_int, _fp, _fp] + [c_int] * 6 + [_fp, _fp]
         L.wgsr_droid_upmask_upsample.restype = c_int
         L.wgsr_droid_upmask_upsample.argtypes = [_fp, _fp, _fp, c_int, _fp, _fp, _fp, _fp] + [c_int] * 5 + [_fp, _fp]
+        # wgsr.frontend.update_heads / graph_agg (csrc/droid_conv3x3.hip)
+        L.wgsr_droid_conv3x3_relu.restype = c_int
+        L.wgsr_droid_conv3x3_relu.argtypes = [_fp, _fp, _fp, c_int, _fp, c_int, c_int, c_int, _fp]
+        L.wgsr_droid_update_heads.restype = c_int
+        L.wgsr_droid_update_heads.argtypes = [_fp] * 10 + [c_int] * 3 + [_fp]
+        L.wgsr_droid_graph_agg.restype = c_int
+        L.wgsr_droid_graph_agg.argtypes = [_fp, _fp, c_int, c_int] + [_fp] * 9 + [c_int, c_int, _fp, _fp]
         L.wgsr_last_error.restype = ctypes.c_char_p
         L.wgsr_last_error.argtypes = []
         L.wgsr_version.restype = ctypes.c_char_p
@@ -390,6 +397,7 @@ EXPORTED_SYMBOLS = (
     "wgsr_droid_ba_workspace_bytes", "wgsr_droid_ba", "wgsr_droid_ba_system", "wgsr_droid_ba_stage_events",
     "wgsr_lie_se3", "wgsr_droid_reproject",
     "wgsr_droid_cvx_upsample", "wgsr_droid_upmask_upsample",
+    "wgsr_droid_conv3x3_relu", "wgsr_droid_update_heads", "wgsr_droid_graph_agg",
 )
 
 VIEW_RECORD_FLOATS = 12   # WGSR_VIEW_RECORD_FLOATS

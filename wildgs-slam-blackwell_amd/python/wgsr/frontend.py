@@ -24,6 +24,12 @@
                         ``cvx_upsample`` / ``upsample_disp`` (droid_net.py:23-45)
                         and ``upsample_from_features``, which computes the mask
                         head (GraphAgg.upmask) inside the same launch
+* ``update_heads``      UpdateModule's delta and weight heads (droid_net.py:
+                        102-115, 141-145) and ``graph_agg``, GraphAgg.forward up
+                        to eta and the features of upmask (droid_net.py:65-77):
+                        3 x 3 convolutions on one fp16 MFMA implicit-GEMM kernel
+                        (csrc/droid_conv3x3.hip); ``pack_conv3x3`` packs a
+                        convolution's parameters for it
 
 poses [num, 7] = (tx, ty, tz, qx, qy, qz, qw), world to camera; disps
 [num, ht, wd]; intrinsics [4] = (fx, fy, cx, cy); device fp32 tensors.
@@ -700,3 +706,241 @@ def upsample_from_features(disps, disps_up, ix, feat, weight, bias, check=True):
                                                 _lib.stream_handle(dev)))
     if check:
         _upsample_raise("upsample_from_features", status)
+
+
+# ---------------------------------------------------------------------------
+# The update operator's output heads and GraphAgg (csrc/droid_conv3x3.hip)
+# ---------------------------------------------------------------------------
+CONV3X3_CIN = 128            # kCvCin
+GRAPH_AGG_STATUS = {1: "an entry of ix is outside [0, num_groups) (WGSR_GRAPH_AGG_BAD_IX)"}
+_PACK_CACHE = {}    # the key of _pack_cached -> (weak references to the parameters, the packed pair)
+_PACK_CACHE_MAX = 16
+
+
+def _pack_layout(w16, b32):
+    """[C_out, 128, 3, 3] float16, [C_out] float32 -> the packed pair of include/wgsr.h"""
+    c_out = w16.size(0)
+    rows = (c_out + 15) // 16 * 16
+    w = torch.zeros(rows, CONV3X3_CIN, 9, dtype=torch.float16, device=w16.device)
+    w[:c_out] = w16.reshape(c_out, CONV3X3_CIN, 9)
+    b = torch.zeros(rows, dtype=torch.float32, device=w16.device)
+    b[:c_out] = b32
+    # [rb, row, ks, lane >> 4, j, tap] -> [rb, tap, ks, lane >> 4, row, j]: lane = 16 (lane >> 4) + row
+    w = w.view(rows // 16, 16, 4, 4, 8, 9).permute(0, 5, 2, 3, 1, 4).contiguous().view(-1)
+    return w, b
+
+
+def _pack_cached(weights, biases, device=None):
+    """The packed pair of the convolutions ``weights`` / ``biases`` stacked along
+    their output channels, on ``device`` (default: where the first weight
+    lies); kept until one of the parameters is written again, as
+    ``_head_param`` keeps its copies."""
+    srcs = tuple(weights) + tuple(biases)
+    for w, b in zip(weights, biases):
+        if w.dim() != 4 or tuple(w.shape[1:]) != (CONV3X3_CIN, 3, 3) or b.numel() != w.size(0):
+            raise ValueError(f"a convolution must be weight (C_out, {CONV3X3_CIN}, 3, 3) and bias (C_out): got "
+                             f"{tuple(w.shape)} and {tuple(b.shape)}")
+    device = torch.device(device) if device is not None else weights[0].device
+    key = tuple((t.data_ptr(), t._version, t.dtype, tuple(t.shape), t.device) for t in srcs) + (device,)
+    hit = _PACK_CACHE.get(key)
+    if hit is not None and all(ref() is t for ref, t in zip(hit[0], srcs)):
+        return hit[1]
+    _PACK_CACHE.pop(key, None)
+    if len(_PACK_CACHE) >= _PACK_CACHE_MAX:
+        _PACK_CACHE.pop(next(iter(_PACK_CACHE)))
+    w16 = torch.cat([w.detach().to(device, torch.float16) for w in weights])
+    b32 = torch.cat([b.detach().to(device, torch.float32).reshape(-1) for b in biases])
+    packed = _pack_layout(w16, b32)
+    _PACK_CACHE[key] = (tuple(weakref.ref(t) for t in srcs), packed)
+    return packed
+
+
+def pack_conv3x3(weight, bias):
+    """A ``Conv2d(128, C_out, 3, padding=1)``'s ``weight`` [C_out, 128, 3, 3]
+    and ``bias`` [C_out] in the order the kernel reads them (include/wgsr.h):
+    ``(packed_w, packed_b)`` on the weight's device (host or GPU).  With R =
+    ceil(C_out / 16), ``packed_w`` is float16 [R * 9 * 4 * 64 * 8],
+
+        packed_w[(((rb 9 + tap) 4 + ks) 64 + lane) 8 + j]
+            = weight[16 rb + (lane & 15), 32 ks + 8 (lane >> 4) + j, tap // 3, tap % 3]
+
+    (weights rounded to float16 once, zeros in the rows past C_out) and
+    ``packed_b`` float32 [16 R], zero past C_out.  The pair is kept until the
+    parameter is written again."""
+    return _pack_cached((weight,), (bias,))
+
+
+def unpack_conv3x3(packed_w, packed_b, c_out):
+    """The inverse of ``pack_conv3x3``: ``(weight [c_out, 128, 3, 3] float16, bias [c_out] float32)``."""
+    rows = packed_b.numel()
+    if rows % 16 or packed_w.numel() != rows * CONV3X3_CIN * 9 or not 0 < c_out <= rows:
+        raise ValueError(f"not a packed pair of {c_out} rows: {packed_w.numel()} weights, {rows} biases")
+    w = packed_w.view(rows // 16, 9, 4, 4, 16, 8).permute(0, 4, 2, 3, 5, 1).reshape(rows, CONV3X3_CIN, 3, 3)
+    return w[:c_out].contiguous(), packed_b[:c_out].clone()
+
+
+class UpdateHeads:
+    """The packed parameters of ``UpdateModule.delta`` / ``.weight`` and of
+    ``GraphAgg`` up to ``eta``, packed once: ``hidden`` (delta.0 stacked on
+    weight.0, 256 rows: both read ``net``, so they run as one launch), ``delta``,
+    ``weight`` (the second layers), ``conv1``, ``conv2``, ``eta``; each a
+    ``(packed_w, packed_b)`` pair of ``pack_conv3x3``."""
+    NAMES = ("delta.0", "delta.2", "weight.0", "weight.2", "agg.conv1", "agg.conv2", "agg.eta.0")
+
+    def __init__(self, hidden, delta, weight, conv1, conv2, eta):
+        self.hidden, self.delta, self.weight, self.conv1, self.conv2, self.eta = hidden, delta, weight, conv1, conv2, eta
+
+    @classmethod
+    def from_state_dict(cls, sd, prefix="update.", device=None):
+        """From the reference modules' ``state_dict`` entries ``<prefix>weight.0/2``,
+        ``delta.0/2``, ``agg.conv1``, ``agg.conv2``, ``agg.eta.0`` (``.weight`` /
+        ``.bias`` each)."""
+        w = {k: sd[f"{prefix}{k}.weight"] for k in cls.NAMES}
+        b = {k: sd[f"{prefix}{k}.bias"] for k in cls.NAMES}
+        one = lambda k: _pack_cached((w[k],), (b[k],), device)  # noqa: E731
+        return cls(_pack_cached((w["delta.0"], w["weight.0"]), (b["delta.0"], b["weight.0"]), device),
+                   one("delta.2"), one("weight.2"), one("agg.conv1"), one("agg.conv2"), one("agg.eta.0"))
+
+
+def _update_params(params, dev):
+    if isinstance(params, UpdateHeads):
+        return params
+    prefix = "update." if "update.delta.0.weight" in params else ""
+    return UpdateHeads.from_state_dict(params, prefix, dev)
+
+
+def _conv_net(who, net):
+    """the checks update_heads / graph_agg / conv3x3_relu share: (device, net [n, 128, ht, wd])"""
+    _inference_only(who, net=net)
+    dev = droid_backends._device_of(net=net)
+    if net.dtype != torch.float16:
+        raise NotImplementedError(f"net: only float16 activations are built (the tracker's autocast), got {net.dtype}")
+    if net.dim() == 5 and net.size(0) == 1:
+        net = net[0]
+    if net.dim() != 4 or net.size(1) != CONV3X3_CIN:
+        raise ValueError(f"net must be (n, {CONV3X3_CIN}, ht, wd): got {tuple(net.shape)}")
+    droid_backends._contiguous(net=net)
+    return dev, net.detach()
+
+
+def _packed_pair(name, pair, dev, rows):
+    w, b = pair
+    droid_backends._device_of(**{name: w, name + "_bias": b})
+    if w.device != dev:
+        raise RuntimeError(f"{name}: expected a tensor on {dev}, got {w.device}")
+    if w.dtype != torch.float16 or b.dtype != torch.float32 or b.numel() != rows or \
+            w.numel() != rows * CONV3X3_CIN * 9 or not w.is_contiguous() or not b.is_contiguous():
+        raise ValueError(f"{name}: not a packed pair of {rows} rows (pack_conv3x3)")
+    return w, b
+
+
+def _out_buffer(name, out, shape, dtype, dev):
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if tuple(out.shape) != tuple(shape) or out.dtype != dtype or out.device != dev or not out.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {dev}")
+    return out
+
+
+def conv3x3_relu(x, packed, out=None):
+    """``relu(conv2d(x, weight, bias, padding=1))`` for ``x`` [n, 128, ht, wd]
+    float16 and ``packed = pack_conv3x3(weight, bias)`` with C_out a multiple of
+    128: float16 [n, C_out, ht, wd], fp32 MFMA accumulation, one rounding --
+    the convolution of this file on its own."""
+    dev, x = _conv_net("conv3x3_relu", x)
+    rows = packed[1].numel()
+    w, b = _packed_pair("packed", packed, dev, rows)
+    n, _, ht, wd = x.shape
+    out = _out_buffer("out", out, (n, rows, ht, wd), torch.float16, dev)
+    if out.numel():
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().wgsr_droid_conv3x3_relu(x.data_ptr(), w.data_ptr(), b.data_ptr(), rows,
+                                                           out.data_ptr(), n, ht, wd, _lib.stream_handle(dev)))
+    return out
+
+
+def update_heads(net, params, out=None):
+    """``UpdateModule``'s ``delta`` and ``weight`` heads on the GRU's output
+    (droid_net.py:141-145): ``net`` [n, 128, ht, wd] float16 (a leading batch
+    dimension of 1 is accepted) -> ``(delta, weight)``, each [n, ht, wd, 2]
+    float32, the permuted form the reference returns.  ``params``: an
+    ``UpdateHeads`` or the modules' ``state_dict``.  Both hidden convolutions
+    run as one 256-row launch whose float16 result (autocast's rounding point)
+    the two second layers read; delta and sigmoid(weight) are fp32 values never
+    rounded to float16.  No host read; capturable in a graph.  ``out``: the
+    pair of buffers to write instead of new ones."""
+    dev, net = _conv_net("update_heads", net)
+    p = _update_params(params, dev)
+    hw, hb = _packed_pair("hidden", p.hidden, dev, 2 * CONV3X3_CIN)
+    dw, db = _packed_pair("delta", p.delta, dev, 16)
+    ww, wb = _packed_pair("weight", p.weight, dev, 16)
+    n, _, ht, wd = net.shape
+    delta = _out_buffer("delta", out[0] if out else None, (n, ht, wd, 2), torch.float32, dev)
+    weight = _out_buffer("weight", out[1] if out else None, (n, ht, wd, 2), torch.float32, dev)
+    if delta.numel():
+        hidden = torch.empty(n, 2 * CONV3X3_CIN, ht, wd, dtype=torch.float16, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().wgsr_droid_update_heads(
+                net.data_ptr(), hw.data_ptr(), hb.data_ptr(), dw.data_ptr(), db.data_ptr(), ww.data_ptr(),
+                wb.data_ptr(), hidden.data_ptr(), delta.data_ptr(), weight.data_ptr(), n, ht, wd,
+                _lib.stream_handle(dev)))
+    return delta, weight
+
+
+def graph_agg(net, ii, params, ix=None, num_groups=None, check=True, out=None):
+    """``GraphAgg.forward`` up to ``eta`` and the input of ``upmask``
+    (droid_net.py:65-77): ``net`` [n, 128, ht, wd] float16 (a leading batch
+    dimension of 1 is accepted), ``ii`` [n] the source frame of each edge ->
+    ``(eta, feat)``: ``eta`` [G, ht, wd] float32 (0.01 softplus, never rounded
+    to float16), ``feat`` [G, 128, ht, wd] float16, which
+    ``upsample_from_features`` takes unchanged:
+
+        eta, feat = graph_agg(net, ii, params)
+        upsample_from_features(video.disps, video.disps_up, torch.unique(ii), feat, upmask_weight, upmask_bias)
+
+    replaces ``GraphAgg.forward`` + ``DepthVideo.upsample``.  With ``ix`` /
+    ``num_groups`` left out the groups are ``torch.unique(ii, sorted=True,
+    return_inverse=True)`` as in the reference, which is one host read (the
+    number of groups).  With both given (``ix`` [n] int64 on the device, each in
+    [0, num_groups); ``ii`` is then unused) there is no host read; the kernel
+    validates ``ix`` and ``check`` reads the status word back and raises
+    ``RuntimeError`` (nothing was written); ``check=False`` skips that read and
+    the call can be captured in a graph.  The mean over a group's edges is an
+    fp32 sum in ascending edge order by one lane per element (bit-identical
+    between runs), rounded to float16 once; a group without an edge gives the
+    mean zero, as ``scatter_mean``."""
+    dev, net = _conv_net("graph_agg", net)
+    p = _update_params(params, dev)
+    c1 = _packed_pair("conv1", p.conv1, dev, CONV3X3_CIN)
+    c2 = _packed_pair("conv2", p.conv2, dev, CONV3X3_CIN)
+    ce = _packed_pair("eta", p.eta, dev, 16)
+    n, _, ht, wd = net.shape
+    if (ix is None) != (num_groups is None):
+        raise ValueError("ix and num_groups are given together or not at all")
+    if ix is None:
+        ii = torch.as_tensor(ii).to(dev).reshape(-1)
+        uniq, ix = torch.unique(ii, sorted=True, return_inverse=True)
+        num_groups = uniq.numel()
+    ix = _upsample_index(ix, dev)
+    G = int(num_groups)
+    if ix.numel() != n:
+        raise ValueError(f"{ix.numel()} group indices for the {n} edges of net")
+    if G < 0 or (G == 0 and n):
+        raise ValueError(f"num_groups = {G} for {n} edges")
+    eta = _out_buffer("eta", out[0] if out else None, (G, ht, wd), torch.float32, dev)
+    feat = _out_buffer("feat", out[1] if out else None, (G, CONV3X3_CIN, ht, wd), torch.float16, dev)
+    if not eta.numel():
+        return eta, feat
+    mean = torch.empty(G, CONV3X3_CIN, ht, wd, dtype=torch.float16, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().wgsr_droid_graph_agg(
+            net.data_ptr(), ix.data_ptr(), n, G, c1[0].data_ptr(), c1[1].data_ptr(), c2[0].data_ptr(),
+            c2[1].data_ptr(), ce[0].data_ptr(), ce[1].data_ptr(), mean.data_ptr(), feat.data_ptr(), eta.data_ptr(),
+            ht, wd, status.data_ptr(), _lib.stream_handle(dev)))
+    if check:
+        word = int(status.item())
+        if word:
+            what = "; ".join(msg for bit, msg in GRAPH_AGG_STATUS.items() if word & bit)
+            raise RuntimeError(f"graph_agg: {what} (status {word}); nothing was written")
+    return eta, feat

@@ -1075,6 +1075,51 @@ int wgsr_droid_graph_agg(const void* net, const int64_t* ix, int n, int G, const
                          const void* conv2_w, const float* conv2_b, const void* eta_w, const float* eta_b,
                          void* mean, void* feat, float* eta, int ht, int wd, uint32_t* status, void* stream);
 
+/* ---- The ConvGRU of the update operator (gru.py:34-48, droid_net.py:138;
+ * csrc/droid_gru.hip; wgsr.frontend.conv_gru):
+ *   glo  = mean over an edge's pixels of sigmoid(w(net)) * net            [n, 128]
+ *   z    = sigmoid(convz([net, inp, corr, flow])     + convz_glo(glo))
+ *   r    = sigmoid(convr([net, inp, corr, flow])     + convr_glo(glo))
+ *   q    = tanh   (convq([r * net, inp, corr, flow]) + convq_glo(glo))
+ *   out  = (1 - z) * net + z * q
+ * net, corr [n, 128, ht, wd], flow [n, 64, ht, wd], fp16 contiguous.  inp: [n,
+ * 128, ht, wd], or with inp_ix [n] int64 the frame buffer [inp_frames, 128,
+ * ht, wd] of which edge e reads frame inp_ix[e] (no gathered copy).  The
+ * concatenations are never written: the K loop of the convolution runs over
+ * the four sources.
+ *
+ * Packed weights, the wide-K form of the layout above (wgsr.frontend.
+ * pack_conv3x3_wide / unpack_conv3x3_wide): for W [C_out, C_in, 3, 3], C_in a
+ * multiple of 32, KS = C_in / 32 and R = ceil(C_out / 16),
+ *   packed[((((rb 9 + tap) KS + ks) 64 + lane) 8 + j)]
+ *     = W[16 rb + (lane & 15)][32 ks + 8 (lane >> 4) + j][tap / 3][tap % 3],
+ * zero where the row is >= C_out; KS = 4 is the layout above.  zr_w: convz
+ * (rows 0 .. 127) stacked on convr (rows 128 .. 255), C_in = 448 in the order
+ * net, inp, corr, flow; q_w: convq.  glo_w, fp16: w [128, 128, 1, 1] packed
+ * the same way with its one tap (8 x 4 x 64 x 8 values), then convz_glo,
+ * convr_glo, convq_glo as they lie, [384][128].  glo_b, fp32 [896]: w's bias
+ * [128], the biases of convz, convr, convq [384], those of convz_glo,
+ * convr_glo, convq_glo [384].  All of them and gbias 16-byte aligned.
+ *
+ * The caller's scratch, readable after the call: gbias [n, 384] fp32,
+ *   gbias[e, 128 k + co] = b_k[co] + (W_k_glo glo[e])[co] + b_k_glo[co]
+ * (k = z, r, q), z [n, 128, ht, wd] fp16 and rnet = r * net [n, 128, ht, wd]
+ * fp16; and glo_part [n, ceil(ht wd / 128), 128] fp32, the sums of the glo
+ * term over chunks of 128 pixels.  Four launches (the chunks' sums, gbias, z
+ * and rnet, out), fp32 inside each; z, rnet and out are the only values
+ * rounded to fp16, once each.  No atomics: two runs give the same bits, and
+ * an edge's result does not depend on the other edges.  out, z, rnet, gbias
+ * and glo_part must overlap neither each other nor an input (WGSR_EINVAL).
+ * Launches only: no allocation, no synchronisation, no host read; n == 0 is a
+ * no-op (status 0).  status (one device word, written by every call): 0, or
+ * WGSR_GRU_BAD_IX when an entry of inp_ix lies outside [0, inp_frames) -- the
+ * call then writes nothing else. */
+#define WGSR_GRU_BAD_IX 1u
+int wgsr_droid_gru(const void* net, const void* inp, const int64_t* inp_ix, int inp_frames, const void* corr,
+                   const void* flow, const void* glo_w, const float* glo_b, const void* zr_w, const void* q_w,
+                   float* gbias, float* glo_part, void* z, void* rnet, void* out, int n, int ht, int wd,
+                   uint32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,12 @@
                         3 x 3 convolutions on one fp16 MFMA implicit-GEMM kernel
                         (csrc/droid_conv3x3.hip); ``pack_conv3x3`` packs a
                         convolution's parameters for it
+* ``conv_gru``          UpdateModule's ConvGRU (gru.py:34-48, droid_net.py:138):
+                        the glo term, then the z / r and the q convolutions over
+                        [net, inp, corr, flow] on the wide-K form of that kernel,
+                        the concatenations never written (csrc/droid_gru.hip);
+                        ``pack_conv3x3_wide`` packs a convolution of any C_in
+                        that is a multiple of 32
 
 poses [num, 7] = (tx, ty, tz, qx, qy, qz, qw), world to camera; disps
 [num, ht, wd]; intrinsics [4] = (fx, fy, cx, cy); device fp32 tensors.
@@ -718,26 +724,32 @@ _PACK_CACHE_MAX = 16
 
 
 def _pack_layout(w16, b32):
-    """[C_out, 128, 3, 3] float16, [C_out] float32 -> the packed pair of include/wgsr.h"""
-    c_out = w16.size(0)
+    """[C_out, C_in, 3, 3] float16 (C_in = 32 KS), [C_out] float32 -> the packed pair of include/wgsr.h"""
+    c_out, c_in = w16.size(0), w16.size(1)
     rows = (c_out + 15) // 16 * 16
-    w = torch.zeros(rows, CONV3X3_CIN, 9, dtype=torch.float16, device=w16.device)
-    w[:c_out] = w16.reshape(c_out, CONV3X3_CIN, 9)
+    w = torch.zeros(rows, c_in, 9, dtype=torch.float16, device=w16.device)
+    w[:c_out] = w16.reshape(c_out, c_in, 9)
     b = torch.zeros(rows, dtype=torch.float32, device=w16.device)
     b[:c_out] = b32
     # [rb, row, ks, lane >> 4, j, tap] -> [rb, tap, ks, lane >> 4, row, j]: lane = 16 (lane >> 4) + row
-    w = w.view(rows // 16, 16, 4, 4, 8, 9).permute(0, 5, 2, 3, 1, 4).contiguous().view(-1)
+    w = w.view(rows // 16, 16, c_in // 32, 4, 8, 9).permute(0, 5, 2, 3, 1, 4).contiguous().view(-1)
     return w, b
 
 
-def _pack_cached(weights, biases, device=None):
+def _pack_cached(weights, biases, device=None, c_in=CONV3X3_CIN):
     """The packed pair of the convolutions ``weights`` / ``biases`` stacked along
     their output channels, on ``device`` (default: where the first weight
     lies); kept until one of the parameters is written again, as
-    ``_head_param`` keeps its copies."""
+    ``_head_param`` keeps its copies.  ``c_in=None``: the wide form, any C_in
+    that is a multiple of 32."""
     srcs = tuple(weights) + tuple(biases)
     for w, b in zip(weights, biases):
-        if w.dim() != 4 or tuple(w.shape[1:]) != (CONV3X3_CIN, 3, 3) or b.numel() != w.size(0):
+        if c_in is None:
+            if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or w.size(1) == 0 or w.size(1) % 32 or \
+                    w.size(1) != weights[0].size(1) or b.numel() != w.size(0):
+                raise ValueError("a convolution must be weight (C_out, C_in, 3, 3) with C_in a positive multiple of 32 "
+                                 f"and bias (C_out): got {tuple(w.shape)} and {tuple(b.shape)}")
+        elif w.dim() != 4 or tuple(w.shape[1:]) != (CONV3X3_CIN, 3, 3) or b.numel() != w.size(0):
             raise ValueError(f"a convolution must be weight (C_out, {CONV3X3_CIN}, 3, 3) and bias (C_out): got "
                              f"{tuple(w.shape)} and {tuple(b.shape)}")
     device = torch.device(device) if device is not None else weights[0].device
@@ -944,3 +956,207 @@ def graph_agg(net, ii, params, ix=None, num_groups=None, check=True, out=None):
             what = "; ".join(msg for bit, msg in GRAPH_AGG_STATUS.items() if word & bit)
             raise RuntimeError(f"graph_agg: {what} (status {word}); nothing was written")
     return eta, feat
+
+
+# ---------------------------------------------------------------------------
+# The update operator's ConvGRU (csrc/droid_gru.hip)
+# ---------------------------------------------------------------------------
+GRU_CIN = 3 * CONV3X3_CIN + CONV3X3_CIN // 2   # net, inp, corr [128 each], flow [64]
+GRU_GLO_CHUNK = 128                            # kGrGloPix: pixels of one partial sum of the glo term
+GRU_STATUS = {1: "an entry of inp_ix is outside the frames of inp (WGSR_GRU_BAD_IX)"}
+
+
+def pack_conv3x3_wide(weight, bias):
+    """``pack_conv3x3`` for a ``Conv2d(C_in, C_out, 3, padding=1)`` of any C_in
+    that is a multiple of 32: with KS = C_in / 32 and R = ceil(C_out / 16),
+    ``packed_w`` is float16 [R * 9 * KS * 64 * 8],
+
+        packed_w[(((rb 9 + tap) KS + ks) 64 + lane) 8 + j]
+            = weight[16 rb + (lane & 15), 32 ks + 8 (lane >> 4) + j, tap // 3, tap % 3]
+
+    and ``packed_b`` float32 [16 R]; C_in = 128 gives the bytes of
+    ``pack_conv3x3``.  The pair is kept until the parameter is written again."""
+    return _pack_cached((weight,), (bias,), c_in=None)
+
+
+def unpack_conv3x3_wide(packed_w, packed_b, c_out, c_in):
+    """The inverse of ``pack_conv3x3_wide``: ``(weight [c_out, c_in, 3, 3] float16, bias [c_out] float32)``."""
+    rows = packed_b.numel()
+    if c_in <= 0 or c_in % 32 or rows % 16 or packed_w.numel() != rows * c_in * 9 or not 0 < c_out <= rows:
+        raise ValueError(f"not a packed pair of {c_out} rows of {c_in} input channels: {packed_w.numel()} weights, "
+                         f"{rows} biases")
+    w = packed_w.view(rows // 16, 9, c_in // 32, 4, 16, 8).permute(0, 4, 2, 3, 5, 1).reshape(rows, c_in, 3, 3)
+    return w[:c_out].contiguous(), packed_b[:c_out].clone()
+
+
+def _gru_glo_cached(weights, biases, device):
+    """``(glo_w, glo_b)`` of include/wgsr.h from ``weights`` = (w, convz_glo,
+    convr_glo, convq_glo) and ``biases`` = (w, convz, convr, convq, convz_glo,
+    convr_glo, convq_glo); kept as ``_pack_cached`` keeps its pairs."""
+    srcs = tuple(weights) + tuple(biases)
+    for w in weights:
+        if w.numel() != CONV3X3_CIN * CONV3X3_CIN or w.size(0) != CONV3X3_CIN:
+            raise ValueError(f"a glo convolution must be weight ({CONV3X3_CIN}, {CONV3X3_CIN}, 1, 1): got "
+                             f"{tuple(w.shape)}")
+    for b in biases:
+        if b.numel() != CONV3X3_CIN:
+            raise ValueError(f"a bias of the GRU must hold {CONV3X3_CIN} values: got {tuple(b.shape)}")
+    key = tuple((t.data_ptr(), t._version, t.dtype, tuple(t.shape), t.device) for t in srcs) + (device, "glo")
+    hit = _PACK_CACHE.get(key)
+    if hit is not None and all(ref() is t for ref, t in zip(hit[0], srcs)):
+        return hit[1]
+    _PACK_CACHE.pop(key, None)
+    if len(_PACK_CACHE) >= _PACK_CACHE_MAX:
+        _PACK_CACHE.pop(next(iter(_PACK_CACHE)))
+    w16 = [w.detach().to(device, torch.float16).reshape(CONV3X3_CIN, CONV3X3_CIN) for w in weights]
+    # w as one tap: [rb, row, ks, lane >> 4, j] -> [rb, ks, lane >> 4, row, j]
+    first = w16[0].view(8, 16, 4, 4, 8).permute(0, 2, 3, 1, 4).contiguous().view(-1)
+    glo_w = torch.cat([first] + [w.reshape(-1) for w in w16[1:]])
+    glo_b = torch.cat([b.detach().to(device, torch.float32).reshape(-1) for b in biases])
+    _PACK_CACHE[key] = (tuple(weakref.ref(t) for t in srcs), (glo_w, glo_b))
+    return glo_w, glo_b
+
+
+class UpdateGRU:
+    """The packed parameters of ``UpdateModule.gru`` (gru.py:19-32), packed
+    once: ``zr`` (convz stacked on convr, 256 rows: both read [net, inp, corr,
+    flow], so they run as one launch) and ``q`` (convq), each a ``(packed_w,
+    packed_b)`` pair of ``pack_conv3x3_wide`` with C_in = 448; ``glo_w`` (w packed
+    as one tap, then convz_glo, convr_glo, convq_glo as they lie) and ``glo_b``
+    (the biases of w, of convz, convr, convq and of the three glo convolutions:
+    float32 [896], the biases the kernels read), the layout of include/wgsr.h."""
+    NAMES = ("convz", "convr", "convq", "w", "convz_glo", "convr_glo", "convq_glo")
+
+    def __init__(self, zr, q, glo_w, glo_b):
+        self.zr, self.q, self.glo_w, self.glo_b = zr, q, glo_w, glo_b
+
+    @classmethod
+    def from_state_dict(cls, sd, prefix="update.gru.", device=None):
+        """From the reference module's ``state_dict`` entries ``<prefix>convz``,
+        ``convr``, ``convq``, ``w``, ``convz_glo``, ``convr_glo``, ``convq_glo``
+        (``.weight`` / ``.bias`` each)."""
+        w = {k: sd[f"{prefix}{k}.weight"] for k in cls.NAMES}
+        b = {k: sd[f"{prefix}{k}.bias"] for k in cls.NAMES}
+        device = torch.device(device) if device is not None else w["convz"].device
+        for k in ("convz", "convr", "convq"):
+            if w[k].dim() != 4 or w[k].size(1) != GRU_CIN or w[k].size(0) != CONV3X3_CIN:
+                raise ValueError(f"{k} must be weight ({CONV3X3_CIN}, {GRU_CIN}, 3, 3): got {tuple(w[k].shape)}")
+        glo = ("w", "convz_glo", "convr_glo", "convq_glo")
+        glo_w, glo_b = _gru_glo_cached([w[k] for k in glo],
+                                       [b[k] for k in ("w", "convz", "convr", "convq") + glo[1:]], device)
+        return cls(_pack_cached((w["convz"], w["convr"]), (b["convz"], b["convr"]), device, c_in=None),
+                   _pack_cached((w["convq"],), (b["convq"],), device, c_in=None), glo_w, glo_b)
+
+
+def _gru_params(params, dev):
+    if isinstance(params, UpdateGRU):
+        return params
+    for prefix in ("update.gru.", "gru.", ""):
+        if f"{prefix}convz.weight" in params:
+            return UpdateGRU.from_state_dict(params, prefix, dev)
+    raise ValueError("params holds no convz.weight under update.gru., gru. or no prefix")
+
+
+def _gru_map(name, t, channels, n, ht, wd, dev):
+    """one activation of conv_gru: float16 [n, channels, ht, wd] on ``dev`` (n None: any number of entries)"""
+    if t.device != dev:
+        droid_backends._device_of(**{name: t})
+        raise RuntimeError(f"{name}: expected a tensor on {dev}, got {t.device}")
+    if t.dtype != torch.float16:
+        raise NotImplementedError(f"{name}: only float16 activations are built (the tracker's autocast), got "
+                                  f"{t.dtype}")
+    if t.dim() == 5 and t.size(0) == 1:
+        t = t[0]
+    if t.dim() != 4 or t.size(1) != channels or tuple(t.shape[2:]) != (ht, wd) or (n is not None and t.size(0) != n):
+        raise ValueError(f"{name} must be ({'F' if n is None else n}, {channels}, {ht}, {wd}): got {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    return t.detach()
+
+
+def _gru_overlap(a, b):
+    la, lb = a.data_ptr(), b.data_ptr()
+    return a.numel() and b.numel() and la < lb + b.numel() * b.element_size() and \
+        lb < la + a.numel() * a.element_size()
+
+
+def conv_gru(net, inp, corr, flow, params, inp_ix=None, check=True, out=None, return_intermediates=False,
+             scratch=None):
+    """``ConvGRU.forward`` as the update operator calls it (droid_net.py:138,
+    ``self.gru(net, inp, corr, flow)``; gru.py:34-48): ``net``, ``corr`` [n, 128,
+    ht, wd] and ``flow`` [n, 64, ht, wd] float16 (a leading batch dimension of 1
+    is accepted) -> ``net'`` float16 [n, 128, ht, wd].  ``inp`` is [n, 128, ht,
+    wd], or with ``inp_ix`` [n] (int64) the per-frame buffer [F, 128, ht, wd] of
+    which edge e reads frame ``inp_ix[e]``, no gathered copy (``video.inps`` and
+    ``iis`` in ``update_lowmem``).  ``params``: an ``UpdateGRU`` or the
+    ``state_dict``.  Four launches: the glo term (two; ``gbias`` [n, 384] float32,
+    the convolutions' biases added), z and r * net (one 256-row convolution over
+    the four sources), then q and the blend.  fp32 inside a launch; z, r * net
+    and net' are the only float16 roundings.  ``return_intermediates``:
+    ``(net', {"gbias", "z", "rnet"})``.  The kernels validate ``inp_ix`` on the
+    device; ``check`` reads the status word back and raises ``RuntimeError``
+    (nothing was written); ``check=False`` skips that read: no synchronisation,
+    and the call can be captured in a graph (``inp_ix`` then has to be a device
+    tensor already).  ``out`` / ``scratch``: the buffer for ``net'`` and the
+    triple ``(gbias, z, rnet)`` to write instead of new ones (a fourth entry:
+    the glo term's partial sums, float32 [n, ceil(ht wd / 128), 128])."""
+    _inference_only("conv_gru", net=net, inp=inp, corr=corr, flow=flow)
+    dev = droid_backends._device_of(net=net, inp=inp, corr=corr, flow=flow)
+    if net.dtype != torch.float16:
+        raise NotImplementedError(f"net: only float16 activations are built (the tracker's autocast), got {net.dtype}")
+    if net.dim() == 5 and net.size(0) == 1:
+        net = net[0]
+    if net.dim() != 4 or net.size(1) != CONV3X3_CIN:
+        raise ValueError(f"net must be (n, {CONV3X3_CIN}, ht, wd): got {tuple(net.shape)}")
+    n, _, ht, wd = net.shape
+    net = _gru_map("net", net, CONV3X3_CIN, n, ht, wd, dev)
+    corr = _gru_map("corr", corr, CONV3X3_CIN, n, ht, wd, dev)
+    flow = _gru_map("flow", flow, CONV3X3_CIN // 2, n, ht, wd, dev)
+    inp = _gru_map("inp", inp, CONV3X3_CIN, None if inp_ix is not None else n, ht, wd, dev)
+    frames = 0
+    if inp_ix is not None:
+        inp_ix = _upsample_index(inp_ix, dev)
+        frames = inp.size(0)
+        if inp_ix.numel() != n:
+            raise ValueError(f"{inp_ix.numel()} entries of inp_ix for the {n} edges of net")
+        if n and not frames:
+            raise ValueError("inp holds no frame")
+    p = _gru_params(params, dev)
+    rows = 2 * CONV3X3_CIN
+    for name, pair, r in (("zr", p.zr, rows), ("q", p.q, CONV3X3_CIN)):
+        w, b = pair
+        droid_backends._device_of(**{name: w})
+        if w.device != dev:
+            raise RuntimeError(f"{name}: expected a tensor on {dev}, got {w.device}")
+        if w.dtype != torch.float16 or w.numel() != r * GRU_CIN * 9 or not w.is_contiguous():
+            raise ValueError(f"{name}: not {r} packed rows of {GRU_CIN} input channels (pack_conv3x3_wide)")
+    if p.glo_w.device != dev or p.glo_b.device != dev:
+        raise RuntimeError(f"glo: expected tensors on {dev}, got {p.glo_w.device} and {p.glo_b.device}")
+    if p.glo_w.dtype != torch.float16 or p.glo_w.numel() != 4 * CONV3X3_CIN ** 2 or p.glo_b.dtype != torch.float32 \
+            or p.glo_b.numel() != 7 * CONV3X3_CIN or not p.glo_w.is_contiguous() or not p.glo_b.is_contiguous():
+        raise ValueError("glo_w / glo_b: not the packed glo parameters (UpdateGRU.from_state_dict)")
+    out = _out_buffer("out", out, (n, CONV3X3_CIN, ht, wd), torch.float16, dev)
+    for name, t in (("net", net), ("inp", inp), ("corr", corr), ("flow", flow)):
+        if _gru_overlap(out, t):
+            raise ValueError(f"out must not overlap {name}")
+    gbias = _out_buffer("gbias", scratch[0] if scratch else None, (n, 3 * CONV3X3_CIN), torch.float32, dev)
+    z = _out_buffer("z", scratch[1] if scratch else None, out.shape, torch.float16, dev)
+    rnet = _out_buffer("rnet", scratch[2] if scratch else None, out.shape, torch.float16, dev)
+    part = _out_buffer("glo_part", scratch[3] if scratch and len(scratch) > 3 else None,
+                       (n, (ht * wd + GRU_GLO_CHUNK - 1) // GRU_GLO_CHUNK, CONV3X3_CIN), torch.float32, dev)
+    if out.numel():
+        status = torch.empty(1, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().wgsr_droid_gru(
+                net.data_ptr(), inp.data_ptr(), _lib.ptr(inp_ix), frames, corr.data_ptr(), flow.data_ptr(),
+                p.glo_w.data_ptr(), p.glo_b.data_ptr(), p.zr[0].data_ptr(), p.q[0].data_ptr(), gbias.data_ptr(),
+                part.data_ptr(), z.data_ptr(), rnet.data_ptr(), out.data_ptr(), n, ht, wd, status.data_ptr(),
+                _lib.stream_handle(dev)))
+        if check and inp_ix is not None:
+            word = int(status.item())
+            if word:
+                what = "; ".join(msg for bit, msg in GRU_STATUS.items() if word & bit)
+                raise RuntimeError(f"conv_gru: {what} (status {word}); nothing was written")
+    if return_intermediates:
+        return out, {"gbias": gbias, "z": z, "rnet": rnet}
+    return out

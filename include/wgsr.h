@@ -1030,14 +1030,18 @@ int wgsr_droid_upmask_upsample(const void* feat, const void* weight, const float
  * rounding point); the heads' outputs (delta, weight, eta) are written as fp32
  * and never rounded to fp16, which is more exact than autocast.
  *
- * Packed parameters (a host-side layout; wgsr.frontend.pack_conv3x3 builds it,
- * unpack_conv3x3 inverts it).  For W [C_out, 128, 3, 3] and R = ceil(C_out /
- * 16) row blocks the packed weights are R x 9 x 4 x 64 x 8 fp16 values:
- *   packed[(((rb 9 + tap) 4 + ks) 64 + lane) 8 + j]
+ * Packed parameters of a 3 x 3 convolution (a host-side layout, shared with
+ * wgsr_droid_gru below; wgsr.frontend.pack_conv3x3_wide builds it,
+ * unpack_conv3x3_wide inverts it).  For W [C_out, C_in, 3, 3], C_in a multiple
+ * of 32, with KS = C_in / 32 K-steps and R = ceil(C_out / 16) row blocks the
+ * packed weights are R x 9 x KS x 64 x 8 fp16 values:
+ *   packed[((((rb 9 + tap) KS + ks) 64 + lane) 8 + j)]
  *     = W[16 rb + (lane & 15)][32 ks + 8 (lane >> 4) + j][tap / 3][tap % 3],
  * zero where the row is >= C_out -- the 16 x 32 MFMA A operand of row block
  * rb, tap and K-step ks as a wave reads it, 16 contiguous bytes per lane.  The
- * packed bias is fp32 [16 R], zero past C_out.  Both 16-byte aligned.
+ * packed bias is fp32 [16 R], zero past C_out.  Both 16-byte aligned.  The
+ * entry points of this section take C_in = 128, KS = 4 (pack_conv3x3 /
+ * unpack_conv3x3).
  *
  * Every call: ht x wd < 2^20, at most 65535 maps; launches only -- no
  * allocation, no synchronisation, no host read -- and capturable in a HIP
@@ -1088,14 +1092,10 @@ int wgsr_droid_graph_agg(const void* net, const int64_t* ix, int n, int G, const
  * concatenations are never written: the K loop of the convolution runs over
  * the four sources.
  *
- * Packed weights, the wide-K form of the layout above (wgsr.frontend.
- * pack_conv3x3_wide / unpack_conv3x3_wide): for W [C_out, C_in, 3, 3], C_in a
- * multiple of 32, KS = C_in / 32 and R = ceil(C_out / 16),
- *   packed[((((rb 9 + tap) KS + ks) 64 + lane) 8 + j)]
- *     = W[16 rb + (lane & 15)][32 ks + 8 (lane >> 4) + j][tap / 3][tap % 3],
- * zero where the row is >= C_out; KS = 4 is the layout above.  zr_w: convz
- * (rows 0 .. 127) stacked on convr (rows 128 .. 255), C_in = 448 in the order
- * net, inp, corr, flow; q_w: convq.  glo_w, fp16: w [128, 128, 1, 1] packed
+ * Packed weights: the layout of the section above with C_in = 448, KS = 14.
+ * zr_w: convz (rows 0 .. 127) stacked on convr (rows 128 .. 255), the input
+ * channels in the order net, inp, corr, flow; q_w: convq.  (No packed bias:
+ * the biases travel in glo_b.)  glo_w, fp16: w [128, 128, 1, 1] packed
  * the same way with its one tap (8 x 4 x 64 x 8 values), then convz_glo,
  * convr_glo, convq_glo as they lie, [384][128].  glo_b, fp32 [896]: w's bias
  * [128], the biases of convz, convr, convq [384], those of convz_glo,

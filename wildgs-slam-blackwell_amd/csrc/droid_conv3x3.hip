@@ -7,23 +7,10 @@
 // [n, 128, ht, wd] fp16 as the reference hands it around (NCHW),
 //   D[co, pixel] = sum_{tap, ci} W[co, ci, tap] X[ci, pixel + tap],
 // by v_mfma_f32_16x16x32_f16 with the output channels as rows (A = weights,
-// B = input, fp32 accumulation), fp32 bias, the epilogue in fp32.
-//
-// Tile.  A workgroup of four waves owns 16 x TY pixels (x by y) of one map, TY
-// = 8 (4 for the group mean, below).  It stages the 18 x (TY + 2) pixels of the
-// tile with its halo, all 128 channels, into LDS, zeros outside the image, transposed on the way in: [pixel][channel]
-// with 272 bytes per pixel, so that the B operand of a lane (pixel lane & 15 of
-// a tile row, 8 consecutive channels) is one ds_read_b128 at any tap offset.
-// (A transposed read of the image as it lies, the idiom of droid_upsample.hip,
-// needs its four pixels per lane 8-byte aligned, which the taps' shifts by one
-// pixel break.)  272 bytes = 68 dwords puts the 16 pixels of a 16-lane group on
-// 16 different 4-dword slots of the 64 banks; the 16-lane groups of
-// ds_read_b128 take lanes of two channel groups, whose slots are one apart, so
-// two of the four groups meet one 2-way conflict: no stride of this layout
-// avoids it (a set of 8 slots is never closed under a shift).  The writes
-// (ds_write_b128, 8 contiguous lanes = 8 consecutive pixels) are conflict-free.
-// A weight fragment is 16 contiguous bytes per lane, 1 KiB per wave, from the
-// packed weights in memory (they stay in L2: 288 KiB per 128 output rows).
+// B = input, fp32 accumulation), fp32 bias, the epilogue in fp32.  The tile of
+// 16 x TY pixels, its staging into LDS, the packed weights (here KS = 4) and
+// the tap x K-step loop are those of droid_conv_tile.h; TY = 8 (4 for the
+// group mean, below), all 128 channels staged at once.
 //
 //   big  (RBW = 4, CBW = 4): wave <-> 4 row blocks (64 output channels) x 4 tile
 //        rows; the workgroup covers 128 output channels per pass and loops
@@ -52,12 +39,7 @@
 //            (threshold 20), fp32, channels last [n, ht, wd, C_out]; not
 //            rounded to fp16, which is more exact than autocast.
 //
-// Packed weights (wgsr.frontend.pack_conv3x3; the layout is part of the ABI,
-// include/wgsr.h): with R = ceil(C_out / 16) row blocks, element
-//   ((((rb 9 + tap) 4 + ks) 64 + lane) 8 + j)
-// = W[16 rb + (lane & 15)][32 ks + 8 (lane >> 4) + j][tap / 3][tap % 3],
-// zero for rows >= C_out: fragment (rb, tap, ks) is the A operand of the wave
-// as it lies.  The bias is fp32 [16 R], zero past C_out.
+// The bias is fp32 [16 R], zero past C_out.
 //
 // Index validation (graph_agg): every workgroup of every launch scans ix and
 // returns before it writes when an entry is outside [0, G); workgroup (0, 0)
@@ -65,27 +47,18 @@
 #include <hip/hip_fp16.h>
 #include <math.h>
 
-#include "wgsr_common.h"
-#include "wgsr_internal.h"
+#include "droid_conv_tile.h"
 
 namespace wgsr {
 
 namespace {
 
-constexpr int kCvCin = 128;
-constexpr int kCvTX = 16;                             // pixels of a tile row; TY rows (8, or 4 for the mean)
-constexpr int kCvHX = kCvTX + 2;                      // with the halo
-constexpr int kCvStride = kCvCin + 8;                 // halfs per staged pixel: 272 bytes
-constexpr int kCvFrag = 64 * 8;                       // halfs of one weight fragment
-constexpr int kCvFragsPerRb = 9 * 4;                  // taps x K-steps
-// dynamic LDS of a tile of TY rows: (TY + 2) x 18 staged pixels + the validation word
-constexpr size_t cv_lds(int ty) { return sizeof(__half) * (size_t)(kCvHX * (ty + 2)) * kCvStride + 16; }
+constexpr int kCvCin = kCtC;                          // C_in: the whole tile is staged at once
+constexpr int kCvKS = kCvCin / 32;                    // K-steps per (row block, tap)
+constexpr int kCvFragsPerRb = 9 * kCvKS;              // taps x K-steps
 
 enum { kRelu16 = 0, kMean16 = 1, kHead32 = 2 };
 enum { kActNone = 0, kActSigmoid = 1, kActEta = 2 };
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct ConvArgs {
   const __half* in;       // [batch, >= 128 channels, ht, wd]: channel 0 of entry 0
@@ -107,55 +80,18 @@ __device__ __forceinline__ float cv_act(float v) {
   return v;
 }
 
-// The tile (x0, y0) of entry `src` with its halo into s_x[pixel][channel]; zero outside the image.
-// Thread <-> (pixel, 8 channels): 8 loads that the wave's lanes continue along x, one 16-byte write.
-template <int TY>
-__device__ __forceinline__ void cv_stage(__half* __restrict__ s_x, const __half* __restrict__ src, int x0, int y0,
-                                         int ht, int wd, int t) {
-  constexpr int kCvHP = kCvHX * (TY + 2);
-  const size_t HW = (size_t)ht * wd;
-  for (int u = t; u < kCvHP * (kCvCin / 8); u += 256) {
-    const int cg = u / kCvHP, hp = u - cg * kCvHP;
-    const int ry = hp / kCvHX, rx = hp - ry * kCvHX;
-    const int y = y0 - 1 + ry, x = x0 - 1 + rx;
-    union {
-      uint4 v;
-      __half h[8];
-    } p;
-    p.v = make_uint4(0, 0, 0, 0);
-    if (y >= 0 && y < ht && x >= 0 && x < wd) {
-      const __half* __restrict__ s = src + (size_t)(8 * cg) * HW + (size_t)y * wd + x;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) p.h[j] = s[(size_t)j * HW];
-    }
-    *reinterpret_cast<uint4*>(s_x + hp * kCvStride + 8 * cg) = p.v;
-  }
-}
-
-// dynamic LDS (16-byte aligned): the staged tile [(TY + 2) x 18][kCvStride] fp16, then the validation word.
+// dynamic LDS: ct_lds(ct_halo(TY)), the staged tile and the validation word.
 // grid (tiles, entries or groups), 256 threads.  Two waves per SIMD: everything in the 256
 // architectural registers (droid_upsample.hip on why).
 template <int RBW, int CBW, int TY, int EPI, int ACT>
 __global__ __launch_bounds__(256, 2) void k_conv3x3(const ConvArgs a) {
-  constexpr int kCvHP = kCvHX * (TY + 2);
   extern __shared__ uint4 s_cv[];
   __half* __restrict__ s_x = reinterpret_cast<__half*>(s_cv);
-  uint32_t* s_bad = reinterpret_cast<uint32_t*>(s_x + kCvHP * kCvStride);
+  uint32_t* s_bad = reinterpret_cast<uint32_t*>(s_x + ct_halo(TY) * kCtStride);
   const int t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
-  if (a.status) {
-    if (t == 0) *s_bad = 0u;
-    __syncthreads();
-    uint32_t bad = 0u;
-    for (int e = t; e < a.n; e += 256) {
-      const int64_t v = a.ix[e];
-      if (v < 0 || v >= a.G) bad = WGSR_GRAPH_AGG_BAD_IX;
-    }
-    if (bad) atomicOr(s_bad, bad);  // (LDS)
-    __syncthreads();
-    const uint32_t st = *s_bad;
-    if (blockIdx.x == 0 && blockIdx.y == 0 && t == 0) *a.status = st;
-    if (st) return;
-  }
+  if (a.status &&
+      ct_bad_ix(s_bad, a.ix, a.n, a.G, WGSR_GRAPH_AGG_BAD_IX, a.status, blockIdx.x == 0 && blockIdx.y == 0, t))
+    return;
   constexpr int WP = TY / CBW;     // waves along the tile's rows
   constexpr int WC = 4 / WP;       // waves along the output channels
   constexpr int PASS_RB = RBW * WC;
@@ -164,12 +100,14 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3(const ConvArgs a) {
   const int i = lane & 15, g = lane >> 4;
   const int b = blockIdx.y;
   const int ty = blockIdx.x / a.tiles_x, tx = blockIdx.x - ty * a.tiles_x;
-  const int x0 = tx * kCvTX, y0 = ty * TY;
+  const int x0 = tx * kCtTX, y0 = ty * TY;
   const int ht = a.ht, wd = a.wd;
   const int x = x0 + i;
+  // pixel (tile row wp CBW, column i) at tap (0, 0), channels 8 g ..
+  const __half* xlane = s_x + (wp * CBW * kCtHX + i) * kCtStride + 8 * g;
 
   if constexpr (EPI != kMean16) {
-    cv_stage<TY>(s_x, a.in + (size_t)b * a.in_bstride, x0, y0, ht, wd, t);
+    ct_stage<TY>(s_x, a.in + (size_t)b * a.in_bstride, kCvCin, x0, y0, ht, wd, t);
     __syncthreads();
   }
   const int passes = a.c_out_pad / (16 * PASS_RB);
@@ -178,7 +116,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3(const ConvArgs a) {
     float4 bias[RBW];
 #pragma unroll
     for (int rb = 0; rb < RBW; ++rb) bias[rb] = *reinterpret_cast<const float4*>(a.b + 16 * (rb0 + rb) + 4 * g);
-    const __half* __restrict__ wfrag = a.w + (size_t)rb0 * kCvFragsPerRb * kCvFrag + 8 * lane;
+    const __half* __restrict__ wfrag = a.w + (size_t)rb0 * kCvFragsPerRb * kCtFrag + 8 * lane;
 
     f32x4 sum[RBW][CBW];
     int count = 0;
@@ -194,7 +132,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3(const ConvArgs a) {
         if (a.ix[e] != (int64_t)b) continue;  // (workgroup-uniform)
         ++count;
         __syncthreads();  // every wave is done with the edge staged before
-        cv_stage<TY>(s_x, a.in + (size_t)e * a.in_bstride, x0, y0, ht, wd, t);
+        ct_stage<TY>(s_x, a.in + (size_t)e * a.in_bstride, kCvCin, x0, y0, ht, wd, t);
         __syncthreads();
       }
       f32x4 acc[RBW][CBW];
@@ -202,27 +140,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3(const ConvArgs a) {
       for (int rb = 0; rb < RBW; ++rb)
 #pragma unroll
         for (int cb = 0; cb < CBW; ++cb) acc[rb][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 1
-      for (int tap = 0; tap < 9; ++tap) {
-        const int ky = tap / 3, kx = tap - 3 * ky;
-        // pixel (tile row wp CBW + cb, column i) shifted by the tap, channels 8 g ..
-        const __half* xrow = s_x + ((wp * CBW + ky) * kCvHX + i + kx) * kCvStride + 8 * g;
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-          f16x8 af[RBW], bf[CBW];
-#pragma unroll
-          for (int rb = 0; rb < RBW; ++rb)
-            af[rb] = *reinterpret_cast<const f16x8*>(wfrag + (size_t)(rb * kCvFragsPerRb + 4 * tap + ks) * kCvFrag);
-#pragma unroll
-          for (int cb = 0; cb < CBW; ++cb)
-            bf[cb] = *reinterpret_cast<const f16x8*>(xrow + cb * kCvHX * kCvStride + 32 * ks);
-#pragma unroll
-          for (int rb = 0; rb < RBW; ++rb)
-#pragma unroll
-            for (int cb = 0; cb < CBW; ++cb)
-              acc[rb][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[rb], bf[cb], acc[rb][cb], 0, 0, 0);
-        }
-      }
+      ct_taps<RBW, CBW, kCvKS>(acc, xlane, wfrag, (size_t)kCvFragsPerRb * kCtFrag, kCvKS, 0, kCvKS);
       // D: row (output channel of the block) 4 g + r in register r, column (pixel of the tile row) i
       if constexpr (EPI == kMean16) {
 #pragma unroll
@@ -285,24 +203,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3x3(const ConvArgs a) {
   }
 }
 
-// The device's LDS limit per workgroup, asked once per call (a host query: no synchronisation).
-int cv_lds_ok(const char* who) {
-  constexpr size_t kCvLds = cv_lds(8);  // the largest tile
-  int dev = 0, limit = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e == hipSuccess) e = hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
-  if (e != hipSuccess) return set_error(WGSR_EHIP, "%s: %s", who, hipGetErrorString(e));
-  if (kCvLds > (size_t)limit)
-    return set_error(WGSR_EINVAL, "%s: the tile needs %zu bytes of LDS, the device gives a workgroup %d", who, kCvLds,
-                     limit);
-  return WGSR_OK;
-}
-
-int cv_shape_ok(const char* who, int batch, int ht, int wd) {
-  if (batch < 0 || batch > 65535 || ht <= 0 || wd <= 0 || (int64_t)ht * wd >= (int64_t(1) << 20))
-    return set_error(WGSR_EINVAL, "%s: bad shape: %d maps of %d x %d", who, batch, ht, wd);
-  return WGSR_OK;
-}
+constexpr size_t kCvLds = ct_lds(ct_halo(8));  // the largest tile
 
 int cv_aligned(const char* who, const void* w, const void* b) {
   if (!w || !b) return set_error(WGSR_EINVAL, "%s: null pointer", who);
@@ -314,15 +215,14 @@ int cv_aligned(const char* who, const void* w, const void* b) {
 // One launch over `batch` maps (or groups); the arguments have been checked.
 template <int RBW, int CBW, int TY, int EPI, int ACT>
 int cv_launch(const char* who, ConvArgs a, int batch, hipStream_t s) {
-  a.tiles_x = (a.wd + kCvTX - 1) / kCvTX;
+  a.tiles_x = (a.wd + kCtTX - 1) / kCtTX;
   a.c_out_pad = (a.c_out + 15) / 16 * 16;
   constexpr int pass_rows = 16 * RBW * (4 / (TY / CBW));
   if (a.c_out_pad % pass_rows != 0)
     return set_error(WGSR_EINVAL, "%s: %d output rows are no multiple of %d", who, a.c_out_pad, pass_rows);
   const dim3 grid((unsigned)(a.tiles_x * ((a.ht + TY - 1) / TY)), (unsigned)batch);
-  hipLaunchKernelGGL((k_conv3x3<RBW, CBW, TY, EPI, ACT>), grid, dim3(256), cv_lds(TY), s, a);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? WGSR_OK : set_error(WGSR_EHIP, "%s: %s", who, hipGetErrorString(e));
+  hipLaunchKernelGGL((k_conv3x3<RBW, CBW, TY, EPI, ACT>), grid, dim3(256), ct_lds(ct_halo(TY)), s, a);
+  return ct_err(who, hipGetLastError());
 }
 
 }  // namespace
@@ -336,13 +236,13 @@ extern "C" {
 int wgsr_droid_conv3x3_relu(const void* x, const void* w_packed, const float* b_packed, int c_out, void* out, int n,
                             int ht, int wd, void* stream) {
   const char* who = "wgsr_droid_conv3x3_relu";
-  if (const int e = cv_shape_ok(who, n, ht, wd)) return e;
+  if (const int e = ct_shape_ok(who, n, ht, wd)) return e;
   if (c_out <= 0 || c_out % 128 != 0)
     return set_error(WGSR_EINVAL, "%s: C_out = %d must be a positive multiple of 128", who, c_out);
   if (n == 0) return WGSR_OK;
   if (!x || !out) return set_error(WGSR_EINVAL, "%s: null pointer", who);
   if (const int e = cv_aligned(who, w_packed, b_packed)) return e;
-  if (const int e = cv_lds_ok(who)) return e;
+  if (const int e = ct_lds_ok(who, kCvLds)) return e;
   ConvArgs a = {};
   a.in = (const __half*)x, a.in_bstride = (int64_t)kCvCin * ht * wd;
   a.w = (const __half*)w_packed, a.b = b_packed, a.c_out = c_out, a.out = out;
@@ -354,13 +254,13 @@ int wgsr_droid_update_heads(const void* net, const void* hidden_w, const float* 
                             const float* delta_b, const void* weight_w, const float* weight_b, void* hidden,
                             float* delta, float* weight, int n, int ht, int wd, void* stream) {
   const char* who = "wgsr_droid_update_heads";
-  if (const int e = cv_shape_ok(who, n, ht, wd)) return e;
+  if (const int e = ct_shape_ok(who, n, ht, wd)) return e;
   if (n == 0) return WGSR_OK;
   if (!net || !hidden || !delta || !weight) return set_error(WGSR_EINVAL, "%s: null pointer", who);
   if (const int e = cv_aligned(who, hidden_w, hidden_b)) return e;
   if (const int e = cv_aligned(who, delta_w, delta_b)) return e;
   if (const int e = cv_aligned(who, weight_w, weight_b)) return e;
-  if (const int e = cv_lds_ok(who)) return e;
+  if (const int e = ct_lds_ok(who, kCvLds)) return e;
   hipStream_t s = (hipStream_t)stream;
   const int64_t HW = (int64_t)ht * wd;
   ConvArgs a = {};
@@ -380,20 +280,19 @@ int wgsr_droid_graph_agg(const void* net, const int64_t* ix, int n, int G, const
                          const void* conv2_w, const float* conv2_b, const void* eta_w, const float* eta_b,
                          void* mean, void* feat, float* eta, int ht, int wd, uint32_t* status, void* stream) {
   const char* who = "wgsr_droid_graph_agg";
-  if (const int e = cv_shape_ok(who, n, ht, wd)) return e;
-  if (const int e = cv_shape_ok(who, G, ht, wd)) return e;
+  if (const int e = ct_shape_ok(who, n, ht, wd)) return e;
+  if (const int e = ct_shape_ok(who, G, ht, wd)) return e;
   if (!status) return set_error(WGSR_EINVAL, "%s: null status", who);
   hipStream_t s = (hipStream_t)stream;
   if (G == 0) {  // (no launch: the status word still has to say so)
     if (n) return set_error(WGSR_EINVAL, "%s: n=%d edges but G=0 groups", who, n);
-    const hipError_t e = hipMemsetAsync(status, 0, sizeof(uint32_t), s);
-    return e == hipSuccess ? WGSR_OK : set_error(WGSR_EHIP, "%s: %s", who, hipGetErrorString(e));
+    return ct_err(who, hipMemsetAsync(status, 0, sizeof(uint32_t), s));
   }
   if ((n && (!net || !ix)) || !mean || !feat || !eta) return set_error(WGSR_EINVAL, "%s: null pointer", who);
   if (const int e = cv_aligned(who, conv1_w, conv1_b)) return e;
   if (const int e = cv_aligned(who, conv2_w, conv2_b)) return e;
   if (const int e = cv_aligned(who, eta_w, eta_b)) return e;
-  if (const int e = cv_lds_ok(who)) return e;
+  if (const int e = ct_lds_ok(who, kCvLds)) return e;
   const int64_t HW = (int64_t)ht * wd;
   ConvArgs a = {};
   a.ix = ix, a.n = n, a.G = G, a.ht = ht, a.wd = wd, a.status = status;

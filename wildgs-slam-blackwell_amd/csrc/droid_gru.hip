@@ -24,8 +24,8 @@
 // bias the two convolution launches add.  No atomics, a fixed order: an
 // edge's result does not depend on the other edges of the call.
 //
-// k_gru_conv, the wide-K form of k_conv3x3 (droid_conv3x3.hip): the same 16 x 8
-// tile, the same [pixel][channel] staging with 272 bytes per pixel, wave <-> 4
+// k_gru_conv, the wide-K form of k_conv3x3 (droid_conv3x3.hip) on the 16 x 8
+// tile, the staging and the tap x K-step loop of droid_conv_tile.h: wave <-> 4
 // row blocks x 4 tile rows, 128 output rows per workgroup; blockIdx.z is the
 // pass of 128 rows (zr: two, convz over convr; q: one).  The K loop runs over
 // up to four sources, each (pointer, 64 or 128 channels, entry stride, optional
@@ -41,9 +41,8 @@
 // sigmoid(v) = 1 / (1 + expf(-v)); tanh(v) = 1 - 2 / (1 + expf(2 v)) (exact
 // limits at both ends: expf -> inf gives 1, expf -> 0 gives -1).
 //
-// Packed weights (wgsr.frontend.pack_conv3x3_wide; include/wgsr.h): element
-//   ((((rb 9 + tap) KS + ks) 64 + lane) 8 + j)
-// = W[16 rb + (lane & 15)][32 ks + 8 (lane >> 4) + j][tap / 3][tap % 3], KS = C_in / 32 = 14.
+// Packed weights (wgsr.frontend.pack_conv3x3_wide): the layout of
+// droid_conv_tile.h with KS = C_in / 32 = 14.
 //
 // Index validation (inp through inp_ix): every workgroup of every launch scans
 // inp_ix and returns before it writes when an entry is outside [0, F);
@@ -51,30 +50,22 @@
 #include <hip/hip_fp16.h>
 #include <math.h>
 
-#include "wgsr_common.h"
-#include "wgsr_internal.h"
+#include "droid_conv_tile.h"
 
 namespace wgsr {
 
 namespace {
 
-constexpr int kGrC = 128;                             // channels of net, and output rows of one pass
-constexpr int kGrTX = 16, kGrTY = 8;                  // the tile
-constexpr int kGrHX = kGrTX + 2;                      // with the halo
-constexpr int kGrHP = kGrHX * (kGrTY + 2);            // staged pixels
-constexpr int kGrStride = kGrC + 8;                   // halfs per staged pixel: 272 bytes
-constexpr int kGrFrag = 64 * 8;                       // halfs of one weight fragment
+constexpr int kGrC = kCtC;                            // channels of net, and output rows of one pass
+constexpr int kGrTY = 8;                              // rows of the tile
 constexpr int kGrGates = 3 * kGrC;                    // columns of gbias
 constexpr int kGrGloPix = 128;                        // pixels of a chunk of k_gru_glo
 // halfs of glo_w: w packed as one tap (8 row blocks x 4 K-steps), then conv{z,r,q}_glo [384][128]
-constexpr int kGrGloPacked = 8 * 4 * kGrFrag;
-constexpr size_t kGrConvLds = sizeof(__half) * (size_t)kGrHP * kGrStride + 16;
-constexpr size_t kGrGloLds = sizeof(__half) * (size_t)kGrGloPix * kGrStride + 16;
+constexpr int kGrGloPacked = 8 * 4 * kCtFrag;
+constexpr size_t kGrConvLds = ct_lds(ct_halo(kGrTY));
+constexpr size_t kGrGloLds = ct_lds(kGrGloPix);
 
 enum { kZR = 0, kQ = 1 };
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct GruSrc {
   const __half* p;        // channel 0 of entry 0
@@ -113,37 +104,19 @@ struct GloArgs {
 __device__ __forceinline__ float gr_sigmoid(float v) { return 1.f / (1.f + expf(-v)); }
 __device__ __forceinline__ float gr_tanh(float v) { return 1.f - 2.f / (1.f + expf(2.f * v)); }
 
-// inp_ix against [0, F): every workgroup scans, the first writes the status; true: return before writing
-__device__ __forceinline__ bool gr_bad_ix(uint32_t* s_bad, const int64_t* __restrict__ ix, int n, int F,
-                                          uint32_t* status, bool first, int t) {
-  if (t == 0) *s_bad = 0u;
-  __syncthreads();
-  uint32_t bad = 0u;
-  if (ix)
-    for (int e = t; e < n; e += 256) {
-      const int64_t v = ix[e];
-      if (v < 0 || v >= F) bad = WGSR_GRU_BAD_IX;
-    }
-  if (bad) atomicOr(s_bad, bad);  // (LDS)
-  __syncthreads();
-  const uint32_t st = *s_bad;
-  if (first && t == 0) *status = st;
-  return st != 0u;
-}
-
-// grid (chunks of 128 pixels, n), 256 threads.  dynamic LDS: the staged chunk [128 pixels][kGrStride] fp16, the
+// grid (chunks of 128 pixels, n), 256 threads.  dynamic LDS: the staged chunk [128 pixels][kCtStride] fp16, the
 // validation word.  part[e][chunk][co] = sum over the chunk's pixels of sigmoid(w(net) + bias) x net.
 __global__ __launch_bounds__(256, 2) void k_gru_glo_part(const GloArgs a) {
   extern __shared__ uint4 s_gr[];
   __half* __restrict__ s_x = reinterpret_cast<__half*>(s_gr);
-  uint32_t* s_bad = reinterpret_cast<uint32_t*>(s_x + kGrGloPix * kGrStride);
+  uint32_t* s_bad = reinterpret_cast<uint32_t*>(s_x + kGrGloPix * kCtStride);
   const int t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
-  if (gr_bad_ix(s_bad, a.inp_ix, a.n, a.F, a.status, blockIdx.x == 0 && blockIdx.y == 0, t)) return;
+  if (ct_bad_ix(s_bad, a.inp_ix, a.n, a.F, WGSR_GRU_BAD_IX, a.status, blockIdx.x == 0 && blockIdx.y == 0, t)) return;
   const int i = lane & 15, g = lane >> 4;
   const int e = blockIdx.y, HW = a.HW, p0 = blockIdx.x * kGrGloPix;
   const __half* __restrict__ net = a.net + (size_t)e * kGrC * HW;
   // wave <-> row blocks 2 wv, 2 wv + 1 (32 output channels) x the 8 pixel blocks of the chunk
-  const __half* __restrict__ wfrag = a.w + (size_t)(2 * wv) * 4 * kGrFrag + 8 * lane;
+  const __half* __restrict__ wfrag = a.w + (size_t)(2 * wv) * 4 * kCtFrag + 8 * lane;
   // thread <-> (pixel, 8 channels): 8 loads that the wave's lanes continue along the pixels, one 16-byte write
   for (int u = t; u < kGrGloPix * (kGrC / 8); u += 256) {
     const int cg = u / kGrGloPix, px = u - cg * kGrGloPix;
@@ -157,7 +130,7 @@ __global__ __launch_bounds__(256, 2) void k_gru_glo_part(const GloArgs a) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) q.h[j] = s[(size_t)j * HW];
     }
-    *reinterpret_cast<uint4*>(s_x + px * kGrStride + 8 * cg) = q.v;
+    *reinterpret_cast<uint4*>(s_x + px * kCtStride + 8 * cg) = q.v;
   }
   __syncthreads();
   f32x4 acc[2][8];
@@ -169,10 +142,10 @@ __global__ __launch_bounds__(256, 2) void k_gru_glo_part(const GloArgs a) {
   for (int ks = 0; ks < 4; ++ks) {
     f16x8 af[2];
 #pragma unroll
-    for (int rb = 0; rb < 2; ++rb) af[rb] = *reinterpret_cast<const f16x8*>(wfrag + (size_t)(4 * rb + ks) * kGrFrag);
+    for (int rb = 0; rb < 2; ++rb) af[rb] = *reinterpret_cast<const f16x8*>(wfrag + (size_t)(4 * rb + ks) * kCtFrag);
 #pragma unroll
     for (int cb = 0; cb < 8; ++cb) {
-      const f16x8 bf = *reinterpret_cast<const f16x8*>(s_x + (16 * cb + i) * kGrStride + 32 * ks + 8 * g);
+      const f16x8 bf = *reinterpret_cast<const f16x8*>(s_x + (16 * cb + i) * kCtStride + 32 * ks + 8 * g);
 #pragma unroll
       for (int rb = 0; rb < 2; ++rb)
         acc[rb][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[rb], bf, acc[rb][cb], 0, 0, 0);
@@ -190,7 +163,7 @@ __global__ __launch_bounds__(256, 2) void k_gru_glo_part(const GloArgs a) {
       float v = 0.f;
 #pragma unroll
       for (int cb = 0; cb < 8; ++cb)
-        v += gr_sigmoid(acc[rb][cb][r] + bs[r]) * __half2float(s_x[(16 * cb + i) * kGrStride + co]);
+        v += gr_sigmoid(acc[rb][cb][r] + bs[r]) * __half2float(s_x[(16 * cb + i) * kCtStride + co]);
 #pragma unroll
       for (int m = 8; m >= 1; m >>= 1) v += __shfl_xor(v, m);
       if (i == 0) a.part[((size_t)e * gridDim.x + blockIdx.x) * kGrC + co] = v;
@@ -204,7 +177,7 @@ __global__ __launch_bounds__(256) void k_gru_glo_finish(const GloArgs a) {
   __shared__ float s_glo[kGrC];
   __shared__ uint32_t s_bad;
   const int t = threadIdx.x;
-  if (gr_bad_ix(&s_bad, a.inp_ix, a.n, a.F, a.status, blockIdx.x == 0, t)) return;
+  if (ct_bad_ix(&s_bad, a.inp_ix, a.n, a.F, WGSR_GRU_BAD_IX, a.status, blockIdx.x == 0, t)) return;
   const int e = blockIdx.x;
   if (t < kGrC) {
     const float* __restrict__ part = a.part + (size_t)e * a.chunks * kGrC + t;
@@ -230,47 +203,29 @@ __global__ __launch_bounds__(256) void k_gru_glo_finish(const GloArgs a) {
   }
 }
 
-// `nch` channels of the tile (x0, y0) of a source's entry with its halo into s_x[pixel][channel]; zero outside the image
-__device__ __forceinline__ void gr_stage(__half* __restrict__ s_x, const __half* __restrict__ src, int nch, int x0,
-                                         int y0, int ht, int wd, int t) {
-  const size_t HW = (size_t)ht * wd;
-  for (int u = t; u < kGrHP * (nch / 8); u += 256) {
-    const int cg = u / kGrHP, hp = u - cg * kGrHP;
-    const int ry = hp / kGrHX, rx = hp - ry * kGrHX;
-    const int y = y0 - 1 + ry, x = x0 - 1 + rx;
-    union {
-      uint4 v;
-      __half h[8];
-    } p;
-    p.v = make_uint4(0, 0, 0, 0);
-    if (y >= 0 && y < ht && x >= 0 && x < wd) {
-      const __half* __restrict__ s = src + (size_t)(8 * cg) * HW + (size_t)y * wd + x;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) p.h[j] = s[(size_t)j * HW];
-    }
-    *reinterpret_cast<uint4*>(s_x + hp * kGrStride + 8 * cg) = p.v;
-  }
-}
-
 // grid (tiles, n, passes of 128 rows), 256 threads.  dynamic LDS: the staged chunk, the validation word.
 // Two waves per SIMD: everything in the 256 architectural registers (droid_upsample.hip on why).
 template <int EPI>
 __global__ __launch_bounds__(256, 2) void k_gru_conv(const GruArgs a) {
   extern __shared__ uint4 s_gr[];
   __half* __restrict__ s_x = reinterpret_cast<__half*>(s_gr);
-  uint32_t* s_bad = reinterpret_cast<uint32_t*>(s_x + kGrHP * kGrStride);
+  uint32_t* s_bad = reinterpret_cast<uint32_t*>(s_x + ct_halo(kGrTY) * kCtStride);
   const int t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
-  if (gr_bad_ix(s_bad, a.inp_ix, a.n, a.F, a.status, blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0, t)) return;
+  if (ct_bad_ix(s_bad, a.inp_ix, a.n, a.F, WGSR_GRU_BAD_IX, a.status,
+                blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0, t))
+    return;
   const int wp = wv & 1, wc = wv >> 1;  // wave <-> tile rows 4 wp .. 4 wp + 3, row blocks 4 wc .. 4 wc + 3 of the pass
   const int i = lane & 15, g = lane >> 4;
   const int b = blockIdx.y, pass = blockIdx.z;
   const int ty = blockIdx.x / a.tiles_x, tx = blockIdx.x - ty * a.tiles_x;
-  const int x0 = tx * kGrTX, y0 = ty * kGrTY;
+  const int x0 = tx * kCtTX, y0 = ty * kGrTY;
   const int ht = a.ht, wd = a.wd;
   const int x = x0 + i;
   const int ksteps = a.ksteps;
-  const __half* __restrict__ wfrag = a.w + (size_t)(8 * pass + 4 * wc) * 9 * ksteps * kGrFrag + 8 * lane;
-  const size_t rbs = (size_t)9 * ksteps * kGrFrag;  // halfs between two row blocks
+  const __half* __restrict__ wfrag = a.w + (size_t)(8 * pass + 4 * wc) * 9 * ksteps * kCtFrag + 8 * lane;
+  const size_t rbs = (size_t)9 * ksteps * kCtFrag;  // halfs between two row blocks
+  // pixel (tile row 4 wp, column i) at tap (0, 0), channels 8 g ..
+  const __half* xlane = s_x + (4 * wp * kCtHX + i) * kCtStride + 8 * g;
 
   f32x4 acc[4][4];
 #pragma unroll
@@ -284,34 +239,10 @@ __global__ __launch_bounds__(256, 2) void k_gru_conv(const GruArgs a) {
     if (nch == 0) continue;  // (workgroup-uniform)
     const int64_t se = a.src[s].ix ? a.src[s].ix[b] : (int64_t)b;
     if (s) __syncthreads();  // every wave is done with the chunk staged before
-    gr_stage(s_x, a.src[s].p + (size_t)se * a.src[s].bstride, nch, x0, y0, ht, wd, t);
+    ct_stage<kGrTY>(s_x, a.src[s].p + (size_t)se * a.src[s].bstride, nch, x0, y0, ht, wd, t);
     __syncthreads();
     const int nks = nch >> 5;  // 2 or 4
-#pragma unroll 1
-    for (int tap = 0; tap < 9; ++tap) {
-      const int ky = tap / 3, kx = tap - 3 * ky;
-      // pixel (tile row 4 wp + cb, column i) shifted by the tap, channels 8 g ..
-      const __half* xrow = s_x + ((4 * wp + ky) * kGrHX + i + kx) * kGrStride + 8 * g;
-      const __half* wtap = wfrag + (size_t)(tap * ksteps + ks0) * kGrFrag;
-#pragma unroll 1
-      for (int k2 = 0; k2 < nks; k2 += 2) {
-#pragma unroll
-        for (int kk = 0; kk < 2; ++kk) {
-          const int ks = k2 + kk;
-          f16x8 af[4], bf[4];
-#pragma unroll
-          for (int rb = 0; rb < 4; ++rb) af[rb] = *reinterpret_cast<const f16x8*>(wtap + rb * rbs + (size_t)ks * kGrFrag);
-#pragma unroll
-          for (int cb = 0; cb < 4; ++cb)
-            bf[cb] = *reinterpret_cast<const f16x8*>(xrow + cb * kGrHX * kGrStride + 32 * ks);
-#pragma unroll
-          for (int rb = 0; rb < 4; ++rb)
-#pragma unroll
-            for (int cb = 0; cb < 4; ++cb)
-              acc[rb][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[rb], bf[cb], acc[rb][cb], 0, 0, 0);
-        }
-      }
-    }
+    ct_taps<4, 4, 0>(acc, xlane, wfrag, rbs, ksteps, ks0, nks);
     ks0 += nks;
   }
   // D: row (output channel of the block) 4 g + r in register r, column (pixel of the tile row) i
@@ -343,23 +274,6 @@ __global__ __launch_bounds__(256, 2) void k_gru_conv(const GruArgs a) {
   }
 }
 
-int gr_err(const char* who, hipError_t e) {
-  return e == hipSuccess ? WGSR_OK : set_error(WGSR_EHIP, "%s: %s", who, hipGetErrorString(e));
-}
-
-// The device's LDS limit per workgroup, asked once per call (a host query: no synchronisation).
-int gr_lds_ok(const char* who) {
-  constexpr size_t need = kGrConvLds > kGrGloLds ? kGrConvLds : kGrGloLds;
-  int dev = 0, limit = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e == hipSuccess) e = hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
-  if (e != hipSuccess) return gr_err(who, e);
-  if (need > (size_t)limit)
-    return set_error(WGSR_EINVAL, "%s: the tile needs %zu bytes of LDS, the device gives a workgroup %d", who, need,
-                     limit);
-  return WGSR_OK;
-}
-
 struct GrRange {
   const char* name;
   uintptr_t lo, hi;
@@ -378,19 +292,18 @@ int wgsr_droid_gru(const void* net, const void* inp, const int64_t* inp_ix, int 
                    float* gbias, float* glo_part, void* z, void* rnet, void* out, int n, int ht, int wd,
                    uint32_t* status, void* stream) {
   const char* who = "wgsr_droid_gru";
-  if (n < 0 || n > 65535 || ht <= 0 || wd <= 0 || (int64_t)ht * wd >= (int64_t(1) << 20))
-    return set_error(WGSR_EINVAL, "%s: bad shape: %d maps of %d x %d", who, n, ht, wd);
+  if (const int e = ct_shape_ok(who, n, ht, wd)) return e;
   if (inp_ix && (inp_frames <= 0 || inp_frames > 65535))
     return set_error(WGSR_EINVAL, "%s: inp_ix with %d frames of inp", who, inp_frames);
   if (!status) return set_error(WGSR_EINVAL, "%s: null status", who);
   hipStream_t s = (hipStream_t)stream;
-  if (n == 0) return gr_err(who, hipMemsetAsync(status, 0, sizeof(uint32_t), s));
+  if (n == 0) return ct_err(who, hipMemsetAsync(status, 0, sizeof(uint32_t), s));
   if (!net || !inp || !corr || !flow || !gbias || !glo_part || !z || !rnet || !out || !glo_w || !glo_b || !zr_w || !q_w)
     return set_error(WGSR_EINVAL, "%s: null pointer", who);
   if ((reinterpret_cast<uintptr_t>(glo_w) | reinterpret_cast<uintptr_t>(glo_b) | reinterpret_cast<uintptr_t>(zr_w) |
        reinterpret_cast<uintptr_t>(q_w) | reinterpret_cast<uintptr_t>(gbias)) & 15)
     return set_error(WGSR_EINVAL, "%s: packed weights, biases and gbias must be 16-byte aligned", who);
-  if (const int e = gr_lds_ok(who)) return e;
+  if (const int e = ct_lds_ok(who, kGrConvLds > kGrGloLds ? kGrConvLds : kGrGloLds)) return e;
   const int64_t HW = (int64_t)ht * wd;
   const uintptr_t map = (uintptr_t)(2 * kGrC * HW);  // bytes of one entry of 128 channels
   const auto range = [](const char* name, const void* p, uintptr_t bytes) {
@@ -417,9 +330,9 @@ int wgsr_droid_gru(const void* net, const void* inp, const int64_t* inp_ix, int 
   ga.part = glo_part, ga.chunks = chunks;
   ga.inp_ix = inp_ix, ga.n = n, ga.F = inp_frames, ga.HW = (int)HW, ga.status = status;
   hipLaunchKernelGGL(k_gru_glo_part, dim3((unsigned)chunks, (unsigned)n), dim3(256), kGrGloLds, s, ga);
-  if (const int e = gr_err(who, hipGetLastError())) return e;
+  if (const int e = ct_err(who, hipGetLastError())) return e;
   hipLaunchKernelGGL(k_gru_glo_finish, dim3((unsigned)n), dim3(256), 0, s, ga);
-  if (const int e = gr_err(who, hipGetLastError())) return e;
+  if (const int e = ct_err(who, hipGetLastError())) return e;
 
   GruArgs a = {};
   a.src[0] = {(const __half*)net, kGrC * HW, nullptr, kGrC};
@@ -429,15 +342,15 @@ int wgsr_droid_gru(const void* net, const void* inp, const int64_t* inp_ix, int 
   a.ksteps = (3 * kGrC + kGrC / 2) / 32;
   a.gbias = gbias, a.net = (const __half*)net;
   a.inp_ix = inp_ix, a.n = n, a.F = inp_frames, a.ht = ht, a.wd = wd, a.status = status;
-  a.tiles_x = (wd + kGrTX - 1) / kGrTX;
+  a.tiles_x = (wd + kCtTX - 1) / kCtTX;
   const unsigned tiles = (unsigned)(a.tiles_x * ((ht + kGrTY - 1) / kGrTY));
   a.w = (const __half*)zr_w, a.gb0 = 0, a.out0 = (__half*)z, a.out1 = (__half*)rnet;
   hipLaunchKernelGGL(k_gru_conv<kZR>, dim3(tiles, (unsigned)n, 2), dim3(256), kGrConvLds, s, a);
-  if (const int e = gr_err(who, hipGetLastError())) return e;
+  if (const int e = ct_err(who, hipGetLastError())) return e;
   a.src[0].p = (const __half*)rnet;
   a.w = (const __half*)q_w, a.gb0 = 2 * kGrC, a.z = (const __half*)z, a.out0 = (__half*)out, a.out1 = nullptr;
   hipLaunchKernelGGL(k_gru_conv<kQ>, dim3(tiles, (unsigned)n, 1), dim3(256), kGrConvLds, s, a);
-  return gr_err(who, hipGetLastError());
+  return ct_err(who, hipGetLastError());
 }
 
 }  // extern "C"

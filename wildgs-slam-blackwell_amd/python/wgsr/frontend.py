@@ -572,10 +572,11 @@ def _upsample_buffers(disps, disps_up):
     return dev, ht, wd
 
 
-def _upsample_raise(who, status):
+def _raise_status(who, status, table):
+    """Reads the status word back (one synchronisation); non-zero: ``RuntimeError`` with ``table``'s messages."""
     word = int(status.item())
     if word:
-        what = "; ".join(msg for bit, msg in UPSAMPLE_STATUS.items() if word & bit)
+        what = "; ".join(msg for bit, msg in table.items() if word & bit)
         raise RuntimeError(f"{who}: {what} (status {word}); nothing was written")
 
 
@@ -588,7 +589,7 @@ def _cvx_launch(who, data, src_index, mask, out, out_index, n, dim, check, dev):
                                              _lib.ptr(out_index), n, data.size(0), out.size(0), data.size(1),
                                              data.size(2), dim, status.data_ptr(), _lib.stream_handle(dev)))
     if check:
-        _upsample_raise(who, status)
+        _raise_status(who, status, UPSAMPLE_STATUS)
 
 
 def cvx_upsample(data, mask):
@@ -711,7 +712,7 @@ def upsample_from_features(disps, disps_up, ix, feat, weight, bias, check=True):
                                                 disps_up.size(0), ht, wd, status.data_ptr(),
                                                 _lib.stream_handle(dev)))
     if check:
-        _upsample_raise("upsample_from_features", status)
+        _raise_status("upsample_from_features", status, UPSAMPLE_STATUS)
 
 
 # ---------------------------------------------------------------------------
@@ -719,8 +720,23 @@ def upsample_from_features(disps, disps_up, ix, feat, weight, bias, check=True):
 # ---------------------------------------------------------------------------
 CONV3X3_CIN = 128            # kCvCin
 GRAPH_AGG_STATUS = {1: "an entry of ix is outside [0, num_groups) (WGSR_GRAPH_AGG_BAD_IX)"}
-_PACK_CACHE = {}    # the key of _pack_cached -> (weak references to the parameters, the packed pair)
+_PACK_CACHE = {}    # the key of _cached -> (weak references to the parameters, what was made of them)
 _PACK_CACHE_MAX = 16
+
+
+def _cached(srcs, tag, make):
+    """``make()`` of the parameters ``srcs``, kept under them and ``tag`` until one
+    of them is written again, as ``_head_param`` keeps its copies."""
+    key = tuple((t.data_ptr(), t._version, t.dtype, tuple(t.shape), t.device) for t in srcs) + tag
+    hit = _PACK_CACHE.get(key)
+    if hit is not None and all(ref() is t for ref, t in zip(hit[0], srcs)):
+        return hit[1]
+    _PACK_CACHE.pop(key, None)
+    if len(_PACK_CACHE) >= _PACK_CACHE_MAX:
+        _PACK_CACHE.pop(next(iter(_PACK_CACHE)))
+    made = make()
+    _PACK_CACHE[key] = (tuple(weakref.ref(t) for t in srcs), made)
+    return made
 
 
 def _pack_layout(w16, b32):
@@ -736,59 +752,38 @@ def _pack_layout(w16, b32):
     return w, b
 
 
-def _pack_cached(weights, biases, device=None, c_in=CONV3X3_CIN):
+def _pack_cached(weights, biases, device=None, c_in=None):
     """The packed pair of the convolutions ``weights`` / ``biases`` stacked along
     their output channels, on ``device`` (default: where the first weight
-    lies); kept until one of the parameters is written again, as
-    ``_head_param`` keeps its copies.  ``c_in=None``: the wide form, any C_in
-    that is a multiple of 32."""
-    srcs = tuple(weights) + tuple(biases)
+    lies), kept by ``_cached``.  C_in is any positive multiple of 32, the same
+    for all of them; ``c_in``: the value it has to have."""
     for w, b in zip(weights, biases):
-        if c_in is None:
-            if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or w.size(1) == 0 or w.size(1) % 32 or \
-                    w.size(1) != weights[0].size(1) or b.numel() != w.size(0):
-                raise ValueError("a convolution must be weight (C_out, C_in, 3, 3) with C_in a positive multiple of 32 "
-                                 f"and bias (C_out): got {tuple(w.shape)} and {tuple(b.shape)}")
-        elif w.dim() != 4 or tuple(w.shape[1:]) != (CONV3X3_CIN, 3, 3) or b.numel() != w.size(0):
-            raise ValueError(f"a convolution must be weight (C_out, {CONV3X3_CIN}, 3, 3) and bias (C_out): got "
+        if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or w.size(1) == 0 or w.size(1) % 32 or \
+                w.size(1) != (c_in or weights[0].size(1)) or b.numel() != w.size(0):
+            raise ValueError("a convolution must be weight (C_out, C_in, 3, 3) with C_in "
+                             f"{f'= {c_in}' if c_in else 'a positive multiple of 32'} and bias (C_out): got "
                              f"{tuple(w.shape)} and {tuple(b.shape)}")
     device = torch.device(device) if device is not None else weights[0].device
-    key = tuple((t.data_ptr(), t._version, t.dtype, tuple(t.shape), t.device) for t in srcs) + (device,)
-    hit = _PACK_CACHE.get(key)
-    if hit is not None and all(ref() is t for ref, t in zip(hit[0], srcs)):
-        return hit[1]
-    _PACK_CACHE.pop(key, None)
-    if len(_PACK_CACHE) >= _PACK_CACHE_MAX:
-        _PACK_CACHE.pop(next(iter(_PACK_CACHE)))
-    w16 = torch.cat([w.detach().to(device, torch.float16) for w in weights])
-    b32 = torch.cat([b.detach().to(device, torch.float32).reshape(-1) for b in biases])
-    packed = _pack_layout(w16, b32)
-    _PACK_CACHE[key] = (tuple(weakref.ref(t) for t in srcs), packed)
-    return packed
+
+    def make():
+        w16 = torch.cat([w.detach().to(device, torch.float16) for w in weights])
+        b32 = torch.cat([b.detach().to(device, torch.float32).reshape(-1) for b in biases])
+        return _pack_layout(w16, b32)
+    return _cached(tuple(weights) + tuple(biases), (device,), make)
 
 
 def pack_conv3x3(weight, bias):
     """A ``Conv2d(128, C_out, 3, padding=1)``'s ``weight`` [C_out, 128, 3, 3]
     and ``bias`` [C_out] in the order the kernel reads them (include/wgsr.h):
-    ``(packed_w, packed_b)`` on the weight's device (host or GPU).  With R =
-    ceil(C_out / 16), ``packed_w`` is float16 [R * 9 * 4 * 64 * 8],
-
-        packed_w[(((rb 9 + tap) 4 + ks) 64 + lane) 8 + j]
-            = weight[16 rb + (lane & 15), 32 ks + 8 (lane >> 4) + j, tap // 3, tap % 3]
-
-    (weights rounded to float16 once, zeros in the rows past C_out) and
-    ``packed_b`` float32 [16 R], zero past C_out.  The pair is kept until the
-    parameter is written again."""
-    return _pack_cached((weight,), (bias,))
+    ``(packed_w, packed_b)`` on the weight's device (host or GPU): the layout
+    of ``pack_conv3x3_wide`` with KS = 4, for no other C_in.  The pair is kept
+    until the parameter is written again."""
+    return _pack_cached((weight,), (bias,), c_in=CONV3X3_CIN)
 
 
 def unpack_conv3x3(packed_w, packed_b, c_out):
     """The inverse of ``pack_conv3x3``: ``(weight [c_out, 128, 3, 3] float16, bias [c_out] float32)``."""
-    rows = packed_b.numel()
-    if rows % 16 or packed_w.numel() != rows * CONV3X3_CIN * 9 or not 0 < c_out <= rows:
-        raise ValueError(f"not a packed pair of {c_out} rows: {packed_w.numel()} weights, {rows} biases")
-    w = packed_w.view(rows // 16, 9, 4, 4, 16, 8).permute(0, 4, 2, 3, 5, 1).reshape(rows, CONV3X3_CIN, 3, 3)
-    return w[:c_out].contiguous(), packed_b[:c_out].clone()
+    return unpack_conv3x3_wide(packed_w, packed_b, c_out, CONV3X3_CIN)
 
 
 class UpdateHeads:
@@ -809,8 +804,8 @@ class UpdateHeads:
         ``.bias`` each)."""
         w = {k: sd[f"{prefix}{k}.weight"] for k in cls.NAMES}
         b = {k: sd[f"{prefix}{k}.bias"] for k in cls.NAMES}
-        one = lambda k: _pack_cached((w[k],), (b[k],), device)  # noqa: E731
-        return cls(_pack_cached((w["delta.0"], w["weight.0"]), (b["delta.0"], b["weight.0"]), device),
+        one = lambda k: _pack_cached((w[k],), (b[k],), device, CONV3X3_CIN)  # noqa: E731
+        return cls(_pack_cached((w["delta.0"], w["weight.0"]), (b["delta.0"], b["weight.0"]), device, CONV3X3_CIN),
                    one("delta.2"), one("weight.2"), one("agg.conv1"), one("agg.conv2"), one("agg.eta.0"))
 
 
@@ -821,28 +816,43 @@ def _update_params(params, dev):
     return UpdateHeads.from_state_dict(params, prefix, dev)
 
 
+def _activation(name, t, channels, dev, n=None, hw=None, not_contiguous=ValueError):
+    """One activation of the convolution calls: float16 [n, channels, ht, wd] on
+    ``dev``, contiguous (a leading batch dimension of 1 is accepted; ``n`` /
+    ``hw`` None: any number of entries / any map size), detached."""
+    if t.device != dev:
+        droid_backends._device_of(**{name: t})
+        raise RuntimeError(f"{name}: expected a tensor on {dev}, got {t.device}")
+    if t.dtype != torch.float16:
+        raise NotImplementedError(f"{name}: only float16 activations are built (the tracker's autocast), got "
+                                  f"{t.dtype}")
+    if t.dim() == 5 and t.size(0) == 1:
+        t = t[0]
+    if t.dim() != 4 or t.size(1) != channels or (hw is not None and tuple(t.shape[2:]) != hw) or \
+            (n is not None and t.size(0) != n):
+        want = ("n" if n is None else n, channels) + (("ht", "wd") if hw is None else hw)
+        raise ValueError(f"{name} must be ({', '.join(map(str, want))}): got {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise not_contiguous(f"{name} must be contiguous")
+    return t.detach()
+
+
 def _conv_net(who, net):
     """the checks update_heads / graph_agg / conv3x3_relu share: (device, net [n, 128, ht, wd])"""
     _inference_only(who, net=net)
     dev = droid_backends._device_of(net=net)
-    if net.dtype != torch.float16:
-        raise NotImplementedError(f"net: only float16 activations are built (the tracker's autocast), got {net.dtype}")
-    if net.dim() == 5 and net.size(0) == 1:
-        net = net[0]
-    if net.dim() != 4 or net.size(1) != CONV3X3_CIN:
-        raise ValueError(f"net must be (n, {CONV3X3_CIN}, ht, wd): got {tuple(net.shape)}")
-    droid_backends._contiguous(net=net)
-    return dev, net.detach()
+    return dev, _activation("net", net, CONV3X3_CIN, dev, not_contiguous=RuntimeError)  # (CHECK_CONTIGUOUS's type)
 
 
-def _packed_pair(name, pair, dev, rows):
+def _packed_pair(name, pair, dev, rows, c_in=CONV3X3_CIN):
+    """``pair`` = (packed_w, packed_b) of ``rows`` rows of ``c_in`` input channels on ``dev``"""
     w, b = pair
     droid_backends._device_of(**{name: w, name + "_bias": b})
     if w.device != dev:
         raise RuntimeError(f"{name}: expected a tensor on {dev}, got {w.device}")
     if w.dtype != torch.float16 or b.dtype != torch.float32 or b.numel() != rows or \
-            w.numel() != rows * CONV3X3_CIN * 9 or not w.is_contiguous() or not b.is_contiguous():
-        raise ValueError(f"{name}: not a packed pair of {rows} rows (pack_conv3x3)")
+            w.numel() != rows * c_in * 9 or not w.is_contiguous() or not b.is_contiguous():
+        raise ValueError(f"{name}: not a packed pair of {rows} rows of {c_in} input channels (pack_conv3x3_wide)")
     return w, b
 
 
@@ -951,10 +961,7 @@ def graph_agg(net, ii, params, ix=None, num_groups=None, check=True, out=None):
             c2[1].data_ptr(), ce[0].data_ptr(), ce[1].data_ptr(), mean.data_ptr(), feat.data_ptr(), eta.data_ptr(),
             ht, wd, status.data_ptr(), _lib.stream_handle(dev)))
     if check:
-        word = int(status.item())
-        if word:
-            what = "; ".join(msg for bit, msg in GRAPH_AGG_STATUS.items() if word & bit)
-            raise RuntimeError(f"graph_agg: {what} (status {word}); nothing was written")
+        _raise_status("graph_agg", status, GRAPH_AGG_STATUS)
     return eta, feat
 
 
@@ -967,16 +974,19 @@ GRU_STATUS = {1: "an entry of inp_ix is outside the frames of inp (WGSR_GRU_BAD_
 
 
 def pack_conv3x3_wide(weight, bias):
-    """``pack_conv3x3`` for a ``Conv2d(C_in, C_out, 3, padding=1)`` of any C_in
-    that is a multiple of 32: with KS = C_in / 32 and R = ceil(C_out / 16),
-    ``packed_w`` is float16 [R * 9 * KS * 64 * 8],
+    """A ``Conv2d(C_in, C_out, 3, padding=1)``'s ``weight`` [C_out, C_in, 3, 3]
+    (C_in a multiple of 32) and ``bias`` [C_out] in the order the kernels read
+    them (include/wgsr.h): ``(packed_w, packed_b)`` on the weight's device (host
+    or GPU).  With KS = C_in / 32 and R = ceil(C_out / 16), ``packed_w`` is
+    float16 [R * 9 * KS * 64 * 8],
 
         packed_w[(((rb 9 + tap) KS + ks) 64 + lane) 8 + j]
             = weight[16 rb + (lane & 15), 32 ks + 8 (lane >> 4) + j, tap // 3, tap % 3]
 
-    and ``packed_b`` float32 [16 R]; C_in = 128 gives the bytes of
-    ``pack_conv3x3``.  The pair is kept until the parameter is written again."""
-    return _pack_cached((weight,), (bias,), c_in=None)
+    (weights rounded to float16 once, zeros in the rows past C_out) and
+    ``packed_b`` float32 [16 R], zero past C_out.  The pair is kept until the
+    parameter is written again."""
+    return _pack_cached((weight,), (bias,))
 
 
 def unpack_conv3x3_wide(packed_w, packed_b, c_out, c_in):
@@ -992,8 +1002,7 @@ def unpack_conv3x3_wide(packed_w, packed_b, c_out, c_in):
 def _gru_glo_cached(weights, biases, device):
     """``(glo_w, glo_b)`` of include/wgsr.h from ``weights`` = (w, convz_glo,
     convr_glo, convq_glo) and ``biases`` = (w, convz, convr, convq, convz_glo,
-    convr_glo, convq_glo); kept as ``_pack_cached`` keeps its pairs."""
-    srcs = tuple(weights) + tuple(biases)
+    convr_glo, convq_glo), kept by ``_cached``."""
     for w in weights:
         if w.numel() != CONV3X3_CIN * CONV3X3_CIN or w.size(0) != CONV3X3_CIN:
             raise ValueError(f"a glo convolution must be weight ({CONV3X3_CIN}, {CONV3X3_CIN}, 1, 1): got "
@@ -1001,20 +1010,14 @@ def _gru_glo_cached(weights, biases, device):
     for b in biases:
         if b.numel() != CONV3X3_CIN:
             raise ValueError(f"a bias of the GRU must hold {CONV3X3_CIN} values: got {tuple(b.shape)}")
-    key = tuple((t.data_ptr(), t._version, t.dtype, tuple(t.shape), t.device) for t in srcs) + (device, "glo")
-    hit = _PACK_CACHE.get(key)
-    if hit is not None and all(ref() is t for ref, t in zip(hit[0], srcs)):
-        return hit[1]
-    _PACK_CACHE.pop(key, None)
-    if len(_PACK_CACHE) >= _PACK_CACHE_MAX:
-        _PACK_CACHE.pop(next(iter(_PACK_CACHE)))
-    w16 = [w.detach().to(device, torch.float16).reshape(CONV3X3_CIN, CONV3X3_CIN) for w in weights]
-    # w as one tap: [rb, row, ks, lane >> 4, j] -> [rb, ks, lane >> 4, row, j]
-    first = w16[0].view(8, 16, 4, 4, 8).permute(0, 2, 3, 1, 4).contiguous().view(-1)
-    glo_w = torch.cat([first] + [w.reshape(-1) for w in w16[1:]])
-    glo_b = torch.cat([b.detach().to(device, torch.float32).reshape(-1) for b in biases])
-    _PACK_CACHE[key] = (tuple(weakref.ref(t) for t in srcs), (glo_w, glo_b))
-    return glo_w, glo_b
+
+    def make():
+        w16 = [w.detach().to(device, torch.float16).reshape(CONV3X3_CIN, CONV3X3_CIN) for w in weights]
+        # w as one tap: [rb, row, ks, lane >> 4, j] -> [rb, ks, lane >> 4, row, j]
+        first = w16[0].view(8, 16, 4, 4, 8).permute(0, 2, 3, 1, 4).contiguous().view(-1)
+        glo_w = torch.cat([first] + [w.reshape(-1) for w in w16[1:]])
+        return glo_w, torch.cat([b.detach().to(device, torch.float32).reshape(-1) for b in biases])
+    return _cached(tuple(weights) + tuple(biases), (device, "glo"), make)
 
 
 class UpdateGRU:
@@ -1044,8 +1047,8 @@ class UpdateGRU:
         glo = ("w", "convz_glo", "convr_glo", "convq_glo")
         glo_w, glo_b = _gru_glo_cached([w[k] for k in glo],
                                        [b[k] for k in ("w", "convz", "convr", "convq") + glo[1:]], device)
-        return cls(_pack_cached((w["convz"], w["convr"]), (b["convz"], b["convr"]), device, c_in=None),
-                   _pack_cached((w["convq"],), (b["convq"],), device, c_in=None), glo_w, glo_b)
+        return cls(_pack_cached((w["convz"], w["convr"]), (b["convz"], b["convr"]), device),
+                   _pack_cached((w["convq"],), (b["convq"],), device), glo_w, glo_b)
 
 
 def _gru_params(params, dev):
@@ -1055,23 +1058,6 @@ def _gru_params(params, dev):
         if f"{prefix}convz.weight" in params:
             return UpdateGRU.from_state_dict(params, prefix, dev)
     raise ValueError("params holds no convz.weight under update.gru., gru. or no prefix")
-
-
-def _gru_map(name, t, channels, n, ht, wd, dev):
-    """one activation of conv_gru: float16 [n, channels, ht, wd] on ``dev`` (n None: any number of entries)"""
-    if t.device != dev:
-        droid_backends._device_of(**{name: t})
-        raise RuntimeError(f"{name}: expected a tensor on {dev}, got {t.device}")
-    if t.dtype != torch.float16:
-        raise NotImplementedError(f"{name}: only float16 activations are built (the tracker's autocast), got "
-                                  f"{t.dtype}")
-    if t.dim() == 5 and t.size(0) == 1:
-        t = t[0]
-    if t.dim() != 4 or t.size(1) != channels or tuple(t.shape[2:]) != (ht, wd) or (n is not None and t.size(0) != n):
-        raise ValueError(f"{name} must be ({'F' if n is None else n}, {channels}, {ht}, {wd}): got {tuple(t.shape)}")
-    if not t.is_contiguous():
-        raise ValueError(f"{name} must be contiguous")
-    return t.detach()
 
 
 def _gru_overlap(a, b):
@@ -1102,17 +1088,11 @@ def conv_gru(net, inp, corr, flow, params, inp_ix=None, check=True, out=None, re
     the glo term's partial sums, float32 [n, ceil(ht wd / 128), 128])."""
     _inference_only("conv_gru", net=net, inp=inp, corr=corr, flow=flow)
     dev = droid_backends._device_of(net=net, inp=inp, corr=corr, flow=flow)
-    if net.dtype != torch.float16:
-        raise NotImplementedError(f"net: only float16 activations are built (the tracker's autocast), got {net.dtype}")
-    if net.dim() == 5 and net.size(0) == 1:
-        net = net[0]
-    if net.dim() != 4 or net.size(1) != CONV3X3_CIN:
-        raise ValueError(f"net must be (n, {CONV3X3_CIN}, ht, wd): got {tuple(net.shape)}")
+    net = _activation("net", net, CONV3X3_CIN, dev)
     n, _, ht, wd = net.shape
-    net = _gru_map("net", net, CONV3X3_CIN, n, ht, wd, dev)
-    corr = _gru_map("corr", corr, CONV3X3_CIN, n, ht, wd, dev)
-    flow = _gru_map("flow", flow, CONV3X3_CIN // 2, n, ht, wd, dev)
-    inp = _gru_map("inp", inp, CONV3X3_CIN, None if inp_ix is not None else n, ht, wd, dev)
+    corr = _activation("corr", corr, CONV3X3_CIN, dev, n, (ht, wd))
+    flow = _activation("flow", flow, CONV3X3_CIN // 2, dev, n, (ht, wd))
+    inp = _activation("inp", inp, CONV3X3_CIN, dev, None if inp_ix is not None else n, (ht, wd))
     frames = 0
     if inp_ix is not None:
         inp_ix = _upsample_index(inp_ix, dev)
@@ -1122,14 +1102,8 @@ def conv_gru(net, inp, corr, flow, params, inp_ix=None, check=True, out=None, re
         if n and not frames:
             raise ValueError("inp holds no frame")
     p = _gru_params(params, dev)
-    rows = 2 * CONV3X3_CIN
-    for name, pair, r in (("zr", p.zr, rows), ("q", p.q, CONV3X3_CIN)):
-        w, b = pair
-        droid_backends._device_of(**{name: w})
-        if w.device != dev:
-            raise RuntimeError(f"{name}: expected a tensor on {dev}, got {w.device}")
-        if w.dtype != torch.float16 or w.numel() != r * GRU_CIN * 9 or not w.is_contiguous():
-            raise ValueError(f"{name}: not {r} packed rows of {GRU_CIN} input channels (pack_conv3x3_wide)")
+    _packed_pair("zr", p.zr, dev, 2 * CONV3X3_CIN, GRU_CIN)  # (the kernels read the biases from glo_b)
+    _packed_pair("q", p.q, dev, CONV3X3_CIN, GRU_CIN)
     if p.glo_w.device != dev or p.glo_b.device != dev:
         raise RuntimeError(f"glo: expected tensors on {dev}, got {p.glo_w.device} and {p.glo_b.device}")
     if p.glo_w.dtype != torch.float16 or p.glo_w.numel() != 4 * CONV3X3_CIN ** 2 or p.glo_b.dtype != torch.float32 \
@@ -1153,10 +1127,7 @@ def conv_gru(net, inp, corr, flow, params, inp_ix=None, check=True, out=None, re
                 part.data_ptr(), z.data_ptr(), rnet.data_ptr(), out.data_ptr(), n, ht, wd, status.data_ptr(),
                 _lib.stream_handle(dev)))
         if check and inp_ix is not None:
-            word = int(status.item())
-            if word:
-                what = "; ".join(msg for bit, msg in GRU_STATUS.items() if word & bit)
-                raise RuntimeError(f"conv_gru: {what} (status {word}); nothing was written")
+            _raise_status("conv_gru", status, GRU_STATUS)
     if return_intermediates:
         return out, {"gbias": gbias, "z": z, "rnet": rnet}
     return out

@@ -1120,6 +1120,52 @@ int wgsr_droid_gru(const void* net, const void* inp, const int64_t* inp_ix, int 
                    float* gbias, float* glo_part, void* z, void* rnet, void* out, int n, int ht, int wd,
                    uint32_t* status, void* stream);
 
+/* ---- The two encoders in front of the ConvGRU (UpdateModule.corr_encoder /
+ * .flow_encoder, droid_net.py:88-100, 136-137; csrc/droid_encoders.hip;
+ * wgsr.frontend.corr_encoder / flow_encoder), each one launch:
+ *   corr [n, 196, ht, wd] fp16 (what wgsr_droid_corr_lookup and
+ *        wgsr_droid_altcorr_forward write)
+ *        -> Conv2d(196, 128, 1 x 1) ReLU, Conv2d(128, 128, 3 x 3, pad 1) ReLU
+ *        -> out [n, 128, ht, wd] fp16
+ *   flow [n, 4, ht, wd] fp32 or fp16 (flow_dtype = WGSR_DTYPE_F32 / _F16; fp32
+ *        is rounded to fp16, round to nearest even, as it is read: autocast's
+ *        cast)
+ *        -> Conv2d(4, 128, 7 x 7, pad 3) ReLU, Conv2d(128, 64, 3 x 3, pad 1) ReLU
+ *        -> out [n, 64, ht, wd] fp16
+ * fp16 weights, fp32 accumulation by v_mfma_f32_16x16x32_f16, fp32 biases.  The
+ * hidden layer is fp16(ReLU(first layer + bias)), zero outside the map (the
+ * second convolution pads the hidden layer), kept in LDS: it never reaches
+ * memory and the ABI takes no scratch for it.  out = fp16(ReLU(second layer +
+ * bias)), rounded once; every element is written.  An entry's result does not
+ * depend on the other entries; two runs give the same bits.  No channel past
+ * 195 of corr is read.
+ *
+ * Packed first layers (wgsr.frontend.pack_conv1x1_196 / pack_conv7x7_4 build
+ * them, unpack_conv1x1_196 / unpack_conv7x7_4 invert them): both have 196
+ * products per output, padded to K = 224 = 7 K-steps of 32 with zero weights,
+ * and 128 rows = 8 row blocks: 8 x 7 x 64 x 8 fp16 values, fragment (rb, ks) the
+ * 16 x 32 MFMA A operand as a wave reads it,
+ *   corr: w1[(((rb 7 + ks) 64 + lane) 8 + j)]
+ *           = W[16 rb + (lane & 15)][32 ks + 8 (lane >> 4) + j], zero past channel 195
+ *   flow: w1[(((rb 7 + ks) 64 + lane) 8 + j)]
+ *           = W[16 rb + (lane & 15)][j & 3][ks][2 (lane >> 4) + (j >> 2)], zero where
+ *             the last index is 7
+ *         (K index 32 ky + 4 kx + ci: one K-step is one kernel row, and a lane's
+ *         8 values are the 4 channels of two adjacent pixels),
+ * b1 fp32 [128].  w2 / b2: the packed second layer of the section above (C_in =
+ * 128, KS = 4; 128 rows for corr, 64 rows = 4 row blocks for flow).  All four
+ * 16-byte aligned.
+ *
+ * ht x wd < 2^20, at most 65535 maps; launches only -- no allocation, no
+ * synchronisation, no host read, no atomics -- and capturable in a HIP graph;
+ * n == 0 is a no-op.  The LDS a workgroup needs (74896 bytes for corr, 52176 for
+ * flow) is checked against the device's limit: an error return, never a
+ * launch. */
+int wgsr_droid_corr_encoder(const void* corr, const void* w1, const float* b1, const void* w2, const float* b2,
+                            void* out, int n, int ht, int wd, void* stream);
+int wgsr_droid_flow_encoder(const void* flow, int flow_dtype, const void* w1, const float* b1, const void* w2,
+                            const float* b2, void* out, int n, int ht, int wd, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

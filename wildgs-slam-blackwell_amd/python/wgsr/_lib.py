@@ -353,6 +353,11 @@ def load():
         # wgsr.frontend.conv_gru (csrc/droid_gru.hip)
         L.wgsr_droid_gru.restype = c_int
         L.wgsr_droid_gru.argtypes = [_fp, _fp, _fp, c_int] + [_fp] * 11 + [c_int] * 3 + [_fp, _fp]
+        # wgsr.frontend.corr_encoder / flow_encoder (csrc/droid_encoders.hip)
+        L.wgsr_droid_corr_encoder.restype = c_int
+        L.wgsr_droid_corr_encoder.argtypes = [_fp] * 6 + [c_int] * 3 + [_fp]
+        L.wgsr_droid_flow_encoder.restype = c_int
+        L.wgsr_droid_flow_encoder.argtypes = [_fp, c_int] + [_fp] * 5 + [c_int] * 3 + [_fp]
         L.wgsr_last_error.restype = ctypes.c_char_p
         L.wgsr_last_error.argtypes = []
         L.wgsr_version.restype = ctypes.c_char_p
@@ -401,7 +406,7 @@ EXPORTED_SYMBOLS = (
     "wgsr_lie_se3", "wgsr_droid_reproject",
     "wgsr_droid_cvx_upsample", "wgsr_droid_upmask_upsample",
     "wgsr_droid_conv3x3_relu", "wgsr_droid_update_heads", "wgsr_droid_graph_agg",
-    "wgsr_droid_gru",
+    "wgsr_droid_gru", "wgsr_droid_corr_encoder", "wgsr_droid_flow_encoder",
 )
 
 VIEW_RECORD_FLOATS = 12   # WGSR_VIEW_RECORD_FLOATS

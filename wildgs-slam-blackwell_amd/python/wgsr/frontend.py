@@ -36,6 +36,12 @@
                         the concatenations never written (csrc/droid_gru.hip);
                         ``pack_conv3x3_wide`` packs a convolution of any C_in
                         that is a multiple of 32
+* ``corr_encoder``      UpdateModule's corr and flow encoders (droid_net.py:88-100,
+  ``flow_encoder``      136-137): one launch each, the first layer's float16
+                        result kept in LDS for the 3 x 3 layer
+                        (csrc/droid_encoders.hip)
+* ``update_operator``   the whole UpdateModule.forward (droid_net.py:120-153): the
+                        composition of the calls above
 
 poses [num, 7] = (tx, ty, tz, qx, qy, qz, qw), world to camera; disps
 [num, ht, wd]; intrinsics [4] = (fx, fy, cx, cy); device fp32 tensors.
@@ -816,14 +822,16 @@ def _update_params(params, dev):
     return UpdateHeads.from_state_dict(params, prefix, dev)
 
 
-def _activation(name, t, channels, dev, n=None, hw=None, not_contiguous=ValueError):
+def _activation(name, t, channels, dev, n=None, hw=None, not_contiguous=ValueError, dtypes=(torch.float16,)):
     """One activation of the convolution calls: float16 [n, channels, ht, wd] on
     ``dev``, contiguous (a leading batch dimension of 1 is accepted; ``n`` /
     ``hw`` None: any number of entries / any map size), detached."""
     if t.device != dev:
         droid_backends._device_of(**{name: t})
         raise RuntimeError(f"{name}: expected a tensor on {dev}, got {t.device}")
-    if t.dtype != torch.float16:
+    if t.dtype not in dtypes:
+        if len(dtypes) > 1:
+            raise NotImplementedError(f"{name} must be float32 or float16, got {t.dtype}")
         raise NotImplementedError(f"{name}: only float16 activations are built (the tracker's autocast), got "
                                   f"{t.dtype}")
     if t.dim() == 5 and t.size(0) == 1:
@@ -1131,3 +1139,245 @@ def conv_gru(net, inp, corr, flow, params, inp_ix=None, check=True, out=None, re
     if return_intermediates:
         return out, {"gbias": gbias, "z": z, "rnet": rnet}
     return out
+
+
+# ---------------------------------------------------------------------------
+# The update operator's corr and flow encoders (csrc/droid_encoders.hip) and
+# the whole operator
+# ---------------------------------------------------------------------------
+CORR_PLANES = 196            # 4 levels x 7 x 7: what corr_lookup / AltCorrBlock write
+FLOW_PLANES = 4
+ENC_HIDDEN = CONV3X3_CIN     # channels of both encoders' hidden layer
+ENC_KS = 7                   # K-steps of a first layer: 196 products padded to 224
+
+
+def _pack_first_cached(weight, bias, shape, device, layout):
+    """The packed pair of a first layer (``layout``: [128, *shape[1:]] float16 ->
+    [rb, row, ks, lane >> 4, j] with zeros in the padded K slots), kept by ``_cached``."""
+    if tuple(weight.shape) != shape or bias.numel() != shape[0]:
+        raise ValueError(f"a first layer must be weight {shape} and bias ({shape[0]}): got {tuple(weight.shape)} and "
+                         f"{tuple(bias.shape)}")
+    device = torch.device(device) if device is not None else weight.device
+
+    def make():
+        w = layout(weight.detach().to(device, torch.float16))
+        # [rb, row, ks, lane >> 4, j] -> [rb, ks, lane >> 4, row, j]: lane = 16 (lane >> 4) + row
+        w = w.reshape(ENC_HIDDEN // 16, 16, ENC_KS, 4, 8).permute(0, 2, 3, 1, 4).contiguous().view(-1)
+        return w, bias.detach().to(device, torch.float32).reshape(-1).contiguous()
+    return _cached((weight, bias), (device, "first", shape), make)
+
+
+def _unpack_first(packed_w, packed_b):
+    if packed_w.numel() != ENC_HIDDEN * 32 * ENC_KS or packed_b.numel() != ENC_HIDDEN:
+        raise ValueError(f"not a packed first layer: {packed_w.numel()} weights, {packed_b.numel()} biases")
+    return packed_w.view(ENC_HIDDEN // 16, ENC_KS, 4, 16, 8).permute(0, 3, 1, 2, 4).reshape(ENC_HIDDEN, 32 * ENC_KS)
+
+
+def pack_conv1x1_196(weight, bias, device=None):
+    """``corr_encoder.0``, a ``Conv2d(196, 128, 1)``: ``weight`` [128, 196, 1, 1]
+    and ``bias`` [128] in the order the kernel reads them (include/wgsr.h):
+    ``packed_w`` float16 [8 * 7 * 64 * 8],
+
+        packed_w[((rb 7 + ks) 64 + lane) 8 + j] = weight[16 rb + (lane & 15), 32 ks + 8 (lane >> 4) + j]
+
+    with zeros past channel 195 (K = 224), and ``packed_b`` float32 [128]."""
+    def layout(w16):
+        w = torch.zeros(ENC_HIDDEN, 32 * ENC_KS, dtype=torch.float16, device=w16.device)
+        w[:, :CORR_PLANES] = w16.reshape(ENC_HIDDEN, CORR_PLANES)
+        return w
+    return _pack_first_cached(weight, bias, (ENC_HIDDEN, CORR_PLANES, 1, 1), device, layout)
+
+
+def unpack_conv1x1_196(packed_w, packed_b):
+    """The inverse of ``pack_conv1x1_196``: ``(weight [128, 196, 1, 1] float16, bias [128] float32)``."""
+    w = _unpack_first(packed_w, packed_b)
+    return w[:, :CORR_PLANES].reshape(ENC_HIDDEN, CORR_PLANES, 1, 1).contiguous(), packed_b.clone()
+
+
+def pack_conv7x7_4(weight, bias, device=None):
+    """``flow_encoder.0``, a ``Conv2d(4, 128, 7, padding=3)``: ``weight`` [128, 4,
+    7, 7] and ``bias`` [128] in the order the kernel reads them (include/wgsr.h):
+    K index 32 ky + 4 kx + ci with kx = 7 a zero pad, so that one K-step is one
+    kernel row: ``packed_w`` float16 [8 * 7 * 64 * 8],
+
+        packed_w[((rb 7 + ks) 64 + lane) 8 + j] = weight[16 rb + (lane & 15), j & 3, ks, 2 (lane >> 4) + (j >> 2)]
+
+    and ``packed_b`` float32 [128]."""
+    def layout(w16):
+        w = torch.zeros(ENC_HIDDEN, 7, 8, FLOW_PLANES, dtype=torch.float16, device=w16.device)
+        w[:, :, :7] = w16.permute(0, 2, 3, 1)  # [row, ky, kx, ci]
+        return w
+    return _pack_first_cached(weight, bias, (ENC_HIDDEN, FLOW_PLANES, 7, 7), device, layout)
+
+
+def unpack_conv7x7_4(packed_w, packed_b):
+    """The inverse of ``pack_conv7x7_4``: ``(weight [128, 4, 7, 7] float16, bias [128] float32)``."""
+    w = _unpack_first(packed_w, packed_b).view(ENC_HIDDEN, 7, 8, FLOW_PLANES)
+    return w[:, :, :7].permute(0, 3, 1, 2).contiguous(), packed_b.clone()
+
+
+class UpdateEncoders:
+    """The packed parameters of ``UpdateModule.corr_encoder`` / ``.flow_encoder``,
+    packed once: ``corr1`` (``pack_conv1x1_196``), ``corr2`` (``pack_conv3x3``, 128
+    rows), ``flow1`` (``pack_conv7x7_4``), ``flow2`` (``pack_conv3x3``, 64 rows);
+    each a ``(packed_w, packed_b)`` pair."""
+    NAMES = ("corr_encoder.0", "corr_encoder.2", "flow_encoder.0", "flow_encoder.2")
+
+    def __init__(self, corr1, corr2, flow1, flow2):
+        self.corr1, self.corr2, self.flow1, self.flow2 = corr1, corr2, flow1, flow2
+
+    @classmethod
+    def from_state_dict(cls, sd, prefix="update.", device=None):
+        """From the reference module's ``state_dict`` entries ``<prefix>corr_encoder.0/2``
+        and ``flow_encoder.0/2`` (``.weight`` / ``.bias`` each)."""
+        w = {k: sd[f"{prefix}{k}.weight"] for k in cls.NAMES}
+        b = {k: sd[f"{prefix}{k}.bias"] for k in cls.NAMES}
+        for k, rows in (("corr_encoder.2", CONV3X3_CIN), ("flow_encoder.2", CONV3X3_CIN // 2)):
+            if w[k].dim() != 4 or w[k].size(0) != rows:
+                raise ValueError(f"{k} must be weight ({rows}, {CONV3X3_CIN}, 3, 3): got {tuple(w[k].shape)}")
+        return cls(pack_conv1x1_196(w["corr_encoder.0"], b["corr_encoder.0"], device),
+                   _pack_cached((w["corr_encoder.2"],), (b["corr_encoder.2"],), device, CONV3X3_CIN),
+                   pack_conv7x7_4(w["flow_encoder.0"], b["flow_encoder.0"], device),
+                   _pack_cached((w["flow_encoder.2"],), (b["flow_encoder.2"],), device, CONV3X3_CIN))
+
+
+def _encoder_params(params, dev):
+    if isinstance(params, UpdateEncoders):
+        return params
+    prefix = "update." if "update.corr_encoder.0.weight" in params else ""
+    return UpdateEncoders.from_state_dict(params, prefix, dev)
+
+
+def _first_pair(name, pair, dev):
+    w, b = pair
+    droid_backends._device_of(**{name: w, name + "_bias": b})
+    if w.device != dev:
+        raise RuntimeError(f"{name}: expected a tensor on {dev}, got {w.device}")
+    if w.dtype != torch.float16 or b.dtype != torch.float32 or b.numel() != ENC_HIDDEN or \
+            w.numel() != ENC_HIDDEN * 32 * ENC_KS or not w.is_contiguous() or not b.is_contiguous():
+        raise ValueError(f"{name}: not a packed first layer (pack_conv1x1_196 / pack_conv7x7_4)")
+    return w, b
+
+
+def _encoder_out(name, out, shape, dev, src):
+    out = _out_buffer("out", out, shape, torch.float16, dev)
+    if _gru_overlap(out, src):
+        raise ValueError(f"out must not overlap {name}")
+    return out
+
+
+def corr_encoder(corr, params, out=None):
+    """``UpdateModule.corr_encoder`` (droid_net.py:88-93, 136): ``corr`` [n, 196,
+    ht, wd] float16, what ``corr_lookup`` / ``CorrBlock`` / ``AltCorrBlock``
+    return (a leading batch dimension of 1 is accepted) -> float16 [n, 128, ht,
+    wd], the ``corr`` argument of ``conv_gru``.  ``params``: an
+    ``UpdateEncoders`` or the modules' ``state_dict``.
+    One launch: the 1 x 1 convolution on each tile with its halo, its float16
+    result (autocast's rounding point, zero outside the map) kept in LDS, the
+    3 x 3 convolution on that; fp32 accumulation, one rounding of the output.
+    No host read; capturable in a graph.  ``out``: the buffer to write instead
+    of a new one."""
+    _inference_only("corr_encoder", corr=corr)
+    dev = droid_backends._device_of(corr=corr)
+    corr = _activation("corr", corr, CORR_PLANES, dev)
+    p = _encoder_params(params, dev)
+    w1, b1 = _first_pair("corr1", p.corr1, dev)
+    w2, b2 = _packed_pair("corr2", p.corr2, dev, CONV3X3_CIN)
+    n, _, ht, wd = corr.shape
+    out = _encoder_out("corr", out, (n, CONV3X3_CIN, ht, wd), dev, corr)
+    if out.numel():
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().wgsr_droid_corr_encoder(
+                corr.data_ptr(), w1.data_ptr(), b1.data_ptr(), w2.data_ptr(), b2.data_ptr(), out.data_ptr(), n, ht, wd,
+                _lib.stream_handle(dev)))
+    return out
+
+
+def flow_encoder(flow, params, out=None):
+    """``UpdateModule.flow_encoder`` (droid_net.py:95-100, 137): ``flow`` [n, 4,
+    ht, wd] float32 (what factor_graph.py passes as ``motn``) or float16 (a
+    leading batch dimension of 1 is accepted) -> float16 [n, 64, ht, wd], the
+    ``flow`` argument of ``conv_gru``.  A float32 input is rounded to float16
+    (round to nearest even) as the kernel reads it, which is autocast's cast:
+    both dtypes of the same values give the same bits.  One launch, as
+    ``corr_encoder``: the 7 x 7 convolution on each tile with its halo, its
+    float16 result kept in LDS (zero outside the map), the 3 x 3 convolution on
+    that.  ``params`` and ``out`` as there."""
+    _inference_only("flow_encoder", flow=flow)
+    dev = droid_backends._device_of(flow=flow)
+    flow = _activation("flow", flow, FLOW_PLANES, dev, dtypes=tuple(droid_backends._DTYPE_TAG))
+    p = _encoder_params(params, dev)
+    w1, b1 = _first_pair("flow1", p.flow1, dev)
+    w2, b2 = _packed_pair("flow2", p.flow2, dev, CONV3X3_CIN // 2)
+    n, _, ht, wd = flow.shape
+    out = _encoder_out("flow", out, (n, CONV3X3_CIN // 2, ht, wd), dev, flow)
+    if out.numel():
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().wgsr_droid_flow_encoder(
+                flow.data_ptr(), droid_backends._DTYPE_TAG[flow.dtype], w1.data_ptr(), b1.data_ptr(), w2.data_ptr(),
+                b2.data_ptr(), out.data_ptr(), n, ht, wd, _lib.stream_handle(dev)))
+    return out
+
+
+class UpdateOperator:
+    """The packed parameters of the whole ``UpdateModule``: ``encoders``
+    (``UpdateEncoders``), ``gru`` (``UpdateGRU``), ``heads`` (``UpdateHeads``)."""
+
+    def __init__(self, encoders, gru, heads):
+        self.encoders, self.gru, self.heads = encoders, gru, heads
+
+    @classmethod
+    def from_state_dict(cls, sd, prefix="update.", device=None):
+        """From the reference's ``state_dict`` entries under ``prefix`` (``DroidNet``'s: "update.")."""
+        return cls(UpdateEncoders.from_state_dict(sd, prefix, device),
+                   UpdateGRU.from_state_dict(sd, prefix + "gru.", device),
+                   UpdateHeads.from_state_dict(sd, prefix, device))
+
+
+def update_operator(net, inp, corr, flow=None, ii=None, params=None, inp_ix=None, num_groups=None, check=True,
+                    out=None):
+    """``UpdateModule.forward`` (droid_net.py:120-153) as one call: ``net`` [n,
+    128, ht, wd] float16, ``inp`` as ``conv_gru`` takes it (with ``inp_ix`` the
+    per-frame buffer), ``corr`` [n, 196, ht, wd] float16, ``flow`` [n, 4, ht, wd]
+    float32 or float16, None: zeros, as in the reference (the motion filter)
+    -> ``(net', delta, weight)``, or with ``ii`` [n] ``(net', delta, weight, eta,
+    feat)``: ``net'`` float16 [n, 128, ht, wd], ``delta`` / ``weight`` float32 [n,
+    ht, wd, 2], ``eta`` float32 [G, ht, wd], ``feat`` float16 [G, 128, ht, wd],
+    which ``upsample_from_features`` takes in place of the reference's upmask.
+    The composition ``corr_encoder``, ``flow_encoder`` -> ``conv_gru`` ->
+    ``update_heads`` -> ``graph_agg``, bit-identical to those calls.  ``params``:
+    an ``UpdateOperator`` or the ``state_dict`` of ``UpdateModule`` /
+    ``DroidNet``.  With ``num_groups`` given, ``ii`` holds each edge's group in
+    [0, num_groups) already (``graph_agg``'s ``ix``) and no ``torch.unique`` runs.
+    ``check=False`` skips the reads of the status words: with ``num_groups`` (or
+    without ``ii``) the whole call then makes no host read and can be captured in
+    a graph.  ``out``: the buffers of the returned tuple to write instead of new
+    ones; a status error leaves those of its call and of the later calls
+    untouched."""
+    if params is None:
+        raise ValueError("params: an UpdateOperator or the state_dict of the update module")
+    if not isinstance(params, UpdateOperator):
+        prefix = "update." if "update.corr_encoder.0.weight" in params else ""
+        params = UpdateOperator.from_state_dict(params, prefix, net.device)
+    if flow is None:
+        lead = net.shape[:-3]
+        flow = torch.zeros(*lead, FLOW_PLANES, *net.shape[-2:], dtype=torch.float32, device=net.device)
+    hw = tuple(net.shape[-2:])
+    for name, t in (("corr", corr), ("flow", flow)):
+        if tuple(t.shape[-2:]) != hw or t.shape[:-3] != net.shape[:-3]:
+            raise ValueError(f"{name} must hold the {tuple(net.shape[:-3])} maps of {hw[0]} x {hw[1]} of net: got "
+                             f"{tuple(t.shape)}")
+    corr = corr_encoder(corr, params.encoders)
+    flow = flow_encoder(flow, params.encoders)
+    if out is not None and len(out) != (3 if ii is None else 5):
+        raise ValueError(f"out must hold the {3 if ii is None else 5} buffers of the returned tuple")
+    net = conv_gru(net, inp, corr, flow, params.gru, inp_ix=inp_ix, check=check, out=out[0] if out else None)
+    delta, weight = update_heads(net, params.heads, out=out[1:3] if out else None)
+    if ii is None:
+        return net, delta, weight
+    if num_groups is None:
+        eta, feat = graph_agg(net, ii, params.heads, out=out[3:] if out else None)
+    else:
+        eta, feat = graph_agg(net, None, params.heads, ix=ii, num_groups=num_groups, check=check,
+                              out=out[3:] if out else None)
+    return net, delta, weight, eta, feat

@@ -1166,6 +1166,76 @@ int wgsr_droid_corr_encoder(const void* corr, const void* w1, const float* b1, c
 int wgsr_droid_flow_encoder(const void* flow, int flow_dtype, const void* w1, const float* b1, const void* w2,
                             const float* b2, void* out, int n, int ht, int wd, void* stream);
 
+/* ---- The tracker's feature and context encoders (DroidNet.fnet / .cnet, the
+ * BasicEncoder of extractor.py:75-141; csrc/droid_basic_encoder.hip;
+ * wgsr.frontend.feature_encoder / context_encoder), launch by launch:
+ *   stem    Conv 7 x 7 stride 2, 3 -> 32; N; ReLU
+ *   layer1  2 x block(32 -> 32); layer2  block(32 -> 64, stride 2), block(64 -> 64);
+ *   layer3  block(64 -> 128, stride 2), block(128 -> 128); head  Conv 1 x 1, 128 -> out
+ *   block(x) = ReLU(x' + ReLU(N(conv2(ReLU(N(conv1(x))))))), with x' = N(Conv 1 x 1
+ *   stride 2 (x)) at stride 2, else x; N an instance norm without parameters
+ *   (biased variance, eps 1e-5; fnet) or the identity (cnet).  Padding k / 2:
+ *   a stride-2 output is ceil(in / 2) pixels.
+ *
+ * Normalise on read.  A convolution writes its raw output R = fp16(acc + bias)
+ * (fp16 operands, fp32 accumulation by v_mfma_f32_16x16x32_f16, fp32 bias) and
+ * its consumer applies N, the ReLU and the residual sum while it stages its
+ * tile, in fp32 with one rounding to fp16:
+ *   A  ReLU(N(R))                      (p null)
+ *   B  ReLU(P + ReLU(N(R)))            (p a stored block output, p_stats null)
+ *   C  ReLU(N(Rd) + ReLU(N(R)))        (p a downsample's raw output, p_stats its statistics)
+ * r_stats null: N is the identity, for r and for p.  A staged pixel outside the
+ * map is zero.  side (stride 1 only; or null): [n, c_in, hi, wi] fp16, the
+ * staged values of the map's own pixels, the same bits.  r and p are [.., c_in,
+ * hi, wi] fp16 with r_frame / p_frame halfs between frames, their statistics
+ * [.., c_in, 2] fp32 (mean, rstd) with *_stats_frame floats between frames, so
+ * that one half of a stacked output can be a source.
+ *
+ * wgsr_droid_be_conv computes rows3 rows of a 3 x 3 convolution (w3: the packed
+ * layout of the sections above with KS = c_in / 32) and then rows1 rows of a
+ * 1 x 1 convolution that reads the centre tap of the same staged tile (w1: that
+ * layout with one tap, ((rb KS + ks) 64 + lane) 8 + j; wgsr.frontend.pack_conv1x1):
+ * at stride 2 the block's downsample, at stride 1 with rows3 = 0 the head.
+ * bias fp32 [rows3 + rows1].  out [n, rows3 + rows1, ho, wo] fp16 with (ho, wo)
+ * = (hi, wi), or their halves rounded up at stride 2.  c_in 32 or 64 (rows
+ * multiples of c_in), or 128 at stride 1 (multiples of 64).  epilogue
+ * WGSR_BE_RAW: out = fp16(acc + bias); WGSR_BE_CNET (c_in 128, rows3 0, rows1
+ * 256): out [n, 128, ho, wo] = fp16(tanh(rows 0 .. 127)), out2 [n, 128, ho, wo] =
+ * fp16(ReLU(rows 128 .. 255)).
+ *
+ * Statistics.  part (or null: none) [n, rows, parts, 3] fp32, parts =
+ * wgsr_droid_be_parts(ho, wo, stride): (count, mean, M2) of the fp16 values as
+ * stored, in-image pixels only, one partial per wave of a tile.
+ * wgsr_droid_be_stats merges them in a fixed order with Chan's formula into
+ * stats [n, rows, 2] = (mean, 1 / sqrt(M2 / count + 1e-5)): no atomics, two
+ * runs give the same bits, a frame does not depend on the others.
+ *
+ * wgsr_droid_be_stem: image [n, 3, H, W] fp32 or fp16 (image_dtype); with mean /
+ * std [3] (both or neither) it reads fp16((x - mean_c) / std_c), computed in
+ * fp32, else fp16(x); zero padding after that.  out [n, 32, ceil(H / 2), ceil(W /
+ * 2)], part as above with stride 1.  Packed stem (wgsr.frontend.pack_stem7x7):
+ * product k = 21 ky + 3 kx + ci, 147 of them padded to K = 160 = 5 K-steps with
+ * zero weights, 2 x 5 x 64 x 8 fp16 values,
+ *   w[((rb 5 + ks) 64 + lane) 8 + j] = W[16 rb + (lane & 15)][ci][ky][kx],
+ *     21 ky + 3 kx + ci = 32 ks + 8 (lane >> 4) + j,
+ * bias fp32 [32].  Packed weights and biases 16-byte aligned.
+ *
+ * Every call: the output map (the stem) or the input map (be_conv) of ht x wd <
+ * 2^20 pixels, at most 65535 frames; one launch -- no allocation, no
+ * synchronisation, no host read -- capturable in a HIP graph; n == 0 is a
+ * no-op.  The LDS a workgroup needs (at most 48960 bytes) is checked against
+ * the device's limit: an error return, never a launch. */
+#define WGSR_BE_RAW 0
+#define WGSR_BE_CNET 1
+int wgsr_droid_be_parts(int ho, int wo, int stride);
+int wgsr_droid_be_stem(const void* image, int image_dtype, const float* mean, const float* std_dev, const void* w,
+                       const float* bias, void* out, float* part, int n, int H, int W, void* stream);
+int wgsr_droid_be_conv(const void* r, int64_t r_frame, const float* r_stats, int64_t r_stats_frame, const void* p,
+                       int64_t p_frame, const float* p_stats, int64_t p_stats_frame, void* side, int c_in,
+                       int stride, const void* w3, int rows3, const void* w1, int rows1, const float* bias,
+                       int epilogue, void* out, void* out2, float* part, int n, int hi, int wi, void* stream);
+int wgsr_droid_be_stats(const float* part, float* stats, int n, int rows, int parts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

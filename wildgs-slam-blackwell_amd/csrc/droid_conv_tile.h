@@ -77,15 +77,16 @@ __device__ __forceinline__ void ct_stage(__half* __restrict__ s_x, const __half*
 }
 
 // One K-step of one tap: RBW weight fragments (rbs halfs apart) and CBW B fragments (one per tile row), then
-// RBW x CBW v_mfma_f32_16x16x32_f16.
-template <int RBW, int CBW>
+// RBW x CBW v_mfma_f32_16x16x32_f16.  PS: halfs per staged pixel; HX: staged pixels per row; SY: staged rows per
+// tile row (the stride of the convolution; droid_basic_encoder.hip): the defaults are the tile described above.
+template <int RBW, int CBW, int PS = kCtStride, int HX = kCtHX, int SY = 1>
 __device__ __forceinline__ void ct_kstep(f32x4 (&acc)[RBW][CBW], const __half* xrow, const __half* wtap, size_t rbs,
                                          int ks) {
   f16x8 af[RBW], bf[CBW];
 #pragma unroll
   for (int rb = 0; rb < RBW; ++rb) af[rb] = *reinterpret_cast<const f16x8*>(wtap + rb * rbs + (size_t)ks * kCtFrag);
 #pragma unroll
-  for (int cb = 0; cb < CBW; ++cb) bf[cb] = *reinterpret_cast<const f16x8*>(xrow + cb * kCtHX * kCtStride + 32 * ks);
+  for (int cb = 0; cb < CBW; ++cb) bf[cb] = *reinterpret_cast<const f16x8*>(xrow + cb * SY * HX * PS + 32 * ks);
 #pragma unroll
   for (int rb = 0; rb < RBW; ++rb)
 #pragma unroll
@@ -98,22 +99,22 @@ __device__ __forceinline__ void ct_kstep(f32x4 (&acc)[RBW][CBW], const __half* x
 // tap 0, K-step 0); rbs: halfs between two row blocks; ksteps: K-steps per (row block, tap) of the packed
 // weights; ks0: the K-step of staged channel 0.  NKS > 0: that many K-steps, unrolled (nks unused); NKS == 0: nks
 // K-steps at run time, an even number, the loop kept rolled outside a pair.
-template <int RBW, int CBW, int NKS>
+template <int RBW, int CBW, int NKS, int PS = kCtStride, int HX = kCtHX, int SY = 1>
 __device__ __forceinline__ void ct_taps(f32x4 (&acc)[RBW][CBW], const __half* xlane, const __half* wlane, size_t rbs,
                                         int ksteps, int ks0, int nks) {
 #pragma unroll 1
   for (int tap = 0; tap < 9; ++tap) {
     const int ky = tap / 3, kx = tap - 3 * ky;
-    const __half* xrow = xlane + (ky * kCtHX + kx) * kCtStride;
+    const __half* xrow = xlane + (ky * HX + kx) * PS;
     const __half* wtap = wlane + (size_t)(tap * ksteps + ks0) * kCtFrag;
     if constexpr (NKS > 0) {
 #pragma unroll
-      for (int ks = 0; ks < NKS; ++ks) ct_kstep<RBW, CBW>(acc, xrow, wtap, rbs, ks);
+      for (int ks = 0; ks < NKS; ++ks) ct_kstep<RBW, CBW, PS, HX, SY>(acc, xrow, wtap, rbs, ks);
     } else {
 #pragma unroll 1
       for (int k2 = 0; k2 < nks; k2 += 2) {
 #pragma unroll
-        for (int kk = 0; kk < 2; ++kk) ct_kstep<RBW, CBW>(acc, xrow, wtap, rbs, k2 + kk);
+        for (int kk = 0; kk < 2; ++kk) ct_kstep<RBW, CBW, PS, HX, SY>(acc, xrow, wtap, rbs, k2 + kk);
       }
     }
   }

@@ -358,6 +358,16 @@ def load():
         L.wgsr_droid_corr_encoder.argtypes = [_fp] * 6 + [c_int] * 3 + [_fp]
         L.wgsr_droid_flow_encoder.restype = c_int
         L.wgsr_droid_flow_encoder.argtypes = [_fp, c_int] + [_fp] * 5 + [c_int] * 3 + [_fp]
+        # wgsr.frontend.feature_encoder / context_encoder (csrc/droid_basic_encoder.hip)
+        L.wgsr_droid_be_parts.restype = c_int
+        L.wgsr_droid_be_parts.argtypes = [c_int] * 3
+        L.wgsr_droid_be_stem.restype = c_int
+        L.wgsr_droid_be_stem.argtypes = [_fp, c_int] + [_fp] * 6 + [c_int] * 3 + [_fp]
+        L.wgsr_droid_be_conv.restype = c_int
+        L.wgsr_droid_be_conv.argtypes = ([_fp, c_i64] * 4 + [_fp, c_int, c_int, _fp, c_int, _fp, c_int, _fp, c_int]
+                                         + [_fp] * 3 + [c_int] * 3 + [_fp])
+        L.wgsr_droid_be_stats.restype = c_int
+        L.wgsr_droid_be_stats.argtypes = [_fp, _fp, c_int, c_int, c_int, _fp]
         L.wgsr_last_error.restype = ctypes.c_char_p
         L.wgsr_last_error.argtypes = []
         L.wgsr_version.restype = ctypes.c_char_p
@@ -407,6 +417,7 @@ EXPORTED_SYMBOLS = (
     "wgsr_droid_cvx_upsample", "wgsr_droid_upmask_upsample",
     "wgsr_droid_conv3x3_relu", "wgsr_droid_update_heads", "wgsr_droid_graph_agg",
     "wgsr_droid_gru", "wgsr_droid_corr_encoder", "wgsr_droid_flow_encoder",
+    "wgsr_droid_be_parts", "wgsr_droid_be_stem", "wgsr_droid_be_conv", "wgsr_droid_be_stats",
 )
 
 VIEW_RECORD_FLOATS = 12   # WGSR_VIEW_RECORD_FLOATS

@@ -42,6 +42,11 @@
                         (csrc/droid_encoders.hip)
 * ``update_operator``   the whole UpdateModule.forward (droid_net.py:120-153): the
                         composition of the calls above
+* ``feature_encoder``   DroidNet.fnet / .cnet (the BasicEncoder of extractor.py:
+  ``context_encoder``   75-141; motion_filter.py:39-48, 61-70): 14 convolution
+                        launches that write each raw map once and apply the
+                        norm, the ReLU and the residual sum as the next launch
+                        stages its tile (csrc/droid_basic_encoder.hip)
 
 poses [num, 7] = (tx, ty, tz, qx, qy, qz, qw), world to camera; disps
 [num, ht, wd]; intrinsics [4] = (fx, fy, cx, cy); device fp32 tensors.
@@ -1381,3 +1386,346 @@ def update_operator(net, inp, corr, flow=None, ii=None, params=None, inp_ix=None
         eta, feat = graph_agg(net, None, params.heads, ix=ii, num_groups=num_groups, check=check,
                               out=out[3:] if out else None)
     return net, delta, weight, eta, feat
+
+
+# ---------------------------------------------------------------------------
+# The feature and context encoders, DroidNet.fnet / .cnet (csrc/droid_basic_encoder.hip)
+# ---------------------------------------------------------------------------
+BE_DIMS = (32, 64, 128)      # channels of the stem / layer1, layer2, layer3
+BE_STEM_KS = 5               # K-steps of the stem: 147 products padded to 160
+BE_STEM_K = 147
+BE_OUT = {"instance": 128, "none": 256}   # the head's rows: fnet; cnet (net stacked on inp)
+BE_LAYERS = ("layer1.0", "layer1.1", "layer2.0", "layer2.1", "layer3.0", "layer3.1")
+# the launches after the stem: the convolution, the raw map it normalises and reads, the second term (a block output
+# X: form B; a downsample's raw output Rd: form C; None: form A), the side output, C_in, stride, the raw map it writes
+BE_LAUNCHES = (("layer1.0.conv1", "R0", None, "X0", 32, 1, "R1"), ("layer1.0.conv2", "R1", None, None, 32, 1, "R2"),
+               ("layer1.1.conv1", "R2", "X0", "X1", 32, 1, "R3"), ("layer1.1.conv2", "R3", None, None, 32, 1, "R4"),
+               ("layer2.0.conv1", "R4", "X1", None, 32, 2, "R5"), ("layer2.0.conv2", "R5", None, None, 64, 1, "R6"),
+               ("layer2.1.conv1", "R6", "Rd5", "X3", 64, 1, "R7"), ("layer2.1.conv2", "R7", None, None, 64, 1, "R8"),
+               ("layer3.0.conv1", "R8", "X3", None, 64, 2, "R9"), ("layer3.0.conv2", "R9", None, None, 128, 1, "R10"),
+               ("layer3.1.conv1", "R10", "Rd9", "X5", 128, 1, "R11"),
+               ("layer3.1.conv2", "R11", None, None, 128, 1, "R12"))
+
+
+def pack_stem7x7(weight, bias, device=None):
+    """The encoders' first layer, a ``Conv2d(3, 32, 7, stride=2, padding=3)``:
+    ``weight`` [32, 3, 7, 7] and ``bias`` [32] in the order the kernel reads them
+    (include/wgsr.h): product k = 21 ky + 3 kx + ci, 147 of them padded to 160 =
+    5 K-steps with zero weights, ``packed_w`` float16 [2 * 5 * 64 * 8],
+
+        packed_w[((rb 5 + ks) 64 + lane) 8 + j] = weight[16 rb + (lane & 15), ci, ky, kx],
+            21 ky + 3 kx + ci = 32 ks + 8 (lane >> 4) + j
+
+    and ``packed_b`` float32 [32].  The pair is kept until the parameter is
+    written again."""
+    _stem_check(weight, bias)
+    device = torch.device(device) if device is not None else weight.device
+    return _cached((weight, bias), (device, "stem"), lambda: _stem_layout(weight, bias, device))
+
+
+def _stem_check(weight, bias):
+    shape = (BE_DIMS[0], 3, 7, 7)
+    if tuple(weight.shape) != shape or bias.numel() != shape[0]:
+        raise ValueError(f"the stem must be weight {shape} and bias ({shape[0]}): got {tuple(weight.shape)} and "
+                         f"{tuple(bias.shape)}")
+
+
+def _stem_layout(weight, bias, device):
+    rows = BE_DIMS[0]
+    w = torch.zeros(rows, 32 * BE_STEM_KS, dtype=torch.float16, device=device)
+    w[:, :BE_STEM_K] = weight.detach().to(device, torch.float16).permute(0, 2, 3, 1).reshape(rows, BE_STEM_K)
+    # [rb, row, ks, lane >> 4, j] -> [rb, ks, lane >> 4, row, j]
+    w = w.view(rows // 16, 16, BE_STEM_KS, 4, 8).permute(0, 2, 3, 1, 4).contiguous().view(-1)
+    return w, bias.detach().to(device, torch.float32).reshape(-1).contiguous()
+
+
+def unpack_stem7x7(packed_w, packed_b):
+    """The inverse of ``pack_stem7x7``: ``(weight [32, 3, 7, 7] float16, bias [32] float32)``."""
+    rows = BE_DIMS[0]
+    if packed_w.numel() != rows * 32 * BE_STEM_KS or packed_b.numel() != rows:
+        raise ValueError(f"not a packed stem: {packed_w.numel()} weights, {packed_b.numel()} biases")
+    w = packed_w.view(rows // 16, BE_STEM_KS, 4, 16, 8).permute(0, 3, 1, 2, 4).reshape(rows, 32 * BE_STEM_KS)
+    return w[:, :BE_STEM_K].reshape(rows, 7, 7, 3).permute(0, 3, 1, 2).contiguous(), packed_b.clone()
+
+
+def pack_conv1x1(weight, bias, device=None):
+    """A ``Conv2d(C_in, C_out, 1)``'s ``weight`` [C_out, C_in, 1, 1] (C_in a multiple
+    of 32, C_out of 16) and ``bias`` [C_out] in the order the kernel reads them
+    (include/wgsr.h): the layout of ``pack_conv3x3_wide`` with one tap, with KS =
+    C_in / 32 ``packed_w`` float16 [C_out / 16 * KS * 64 * 8],
+
+        packed_w[((rb KS + ks) 64 + lane) 8 + j] = weight[16 rb + (lane & 15), 32 ks + 8 (lane >> 4) + j]
+
+    and ``packed_b`` float32 [C_out].  The pair is kept until the parameter is
+    written again."""
+    _conv1x1_check(weight, bias)
+    device = torch.device(device) if device is not None else weight.device
+    return _cached((weight, bias), (device, "1x1"), lambda: _conv1x1_layout(weight, bias, device))
+
+
+def _conv1x1_check(weight, bias):
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (1, 1) or weight.size(1) == 0 or weight.size(1) % 32 or \
+            weight.size(0) == 0 or weight.size(0) % 16 or bias.numel() != weight.size(0):
+        raise ValueError("a 1 x 1 convolution must be weight (C_out, C_in, 1, 1) with C_in a positive multiple of 32, "
+                         f"C_out of 16, and bias (C_out): got {tuple(weight.shape)} and {tuple(bias.shape)}")
+
+
+def _conv1x1_layout(weight, bias, device):
+    c_out, c_in = weight.size(0), weight.size(1)
+    w = weight.detach().to(device, torch.float16).reshape(c_out // 16, 16, c_in // 32, 4, 8)
+    return (w.permute(0, 2, 3, 1, 4).contiguous().view(-1),
+            bias.detach().to(device, torch.float32).reshape(-1).contiguous())
+
+
+def unpack_conv1x1(packed_w, packed_b, c_in):
+    """The inverse of ``pack_conv1x1``: ``(weight [C_out, c_in, 1, 1] float16, bias [C_out] float32)``."""
+    rows = packed_b.numel()
+    if c_in <= 0 or c_in % 32 or rows == 0 or rows % 16 or packed_w.numel() != rows * c_in:
+        raise ValueError(f"not a packed 1 x 1 convolution of {c_in} input channels: {packed_w.numel()} weights, "
+                         f"{rows} biases")
+    w = packed_w.view(rows // 16, c_in // 32, 4, 16, 8).permute(0, 3, 1, 2, 4).reshape(rows, c_in, 1, 1)
+    return w.contiguous(), packed_b.clone()
+
+
+class BasicEncoder:
+    """The packed parameters of a ``BasicEncoder`` (extractor.py:75-141;
+    ``DroidNet.fnet`` with ``norm="instance"``, ``.cnet`` with ``norm="none"``),
+    packed once: ``stem`` (``pack_stem7x7``), ``head`` (``pack_conv1x1``, 128 or
+    256 rows) and ``convs``, per residual block ``layerL.B`` the launches
+    ``conv1`` and ``conv2`` as ``(w3, w1, bias, rows3, rows1)``: ``w3`` the 3 x 3
+    convolution (``pack_conv3x3_wide``), ``w1`` the block's 1 x 1 downsample
+    (``pack_conv1x1``; ``layer2.0`` and ``layer3.0`` only, else None), ``bias``
+    float32 [rows3 + rows1]."""
+
+    def __init__(self, norm, stem, convs, head):
+        self.norm, self.stem, self.convs, self.head = norm, stem, convs, head
+        self.out_dim = BE_OUT[norm]
+        # (w3, rows3, w1, rows1, bias) of each launch as wgsr_droid_be_conv takes them
+        self.args = {k: (w3.data_ptr(), rows3, _lib.ptr(w1), rows1, bias.data_ptr())
+                     for k, (w3, w1, bias, rows3, rows1) in convs.items()}
+
+    @classmethod
+    def from_state_dict(cls, sd, prefix="fnet.", norm="instance", device=None):
+        """From the reference module's ``state_dict`` entries ``<prefix>conv1``,
+        ``layer1.0.conv1`` .. ``layer3.1.conv2``, ``layer2.0.downsample.0``,
+        ``layer3.0.downsample.0`` and ``conv2`` (``.weight`` / ``.bias`` each;
+        ``DroidNet``'s prefixes are "fnet." and "cnet.", the module's own "")."""
+        if norm not in BE_OUT:
+            raise ValueError(f"norm must be 'instance' (fnet) or 'none' (cnet): got {norm!r} (batch and group norm are "
+                             "not built)")
+        get = lambda k: (sd[f"{prefix}{k}.weight"], sd[f"{prefix}{k}.bias"])  # noqa: E731
+        device = torch.device(device) if device is not None else get("conv1")[0].device
+        _stem_check(*get("conv1"))
+        names, c_in = ["conv1"], BE_DIMS[0]
+        for name in BE_LAYERS:
+            c_out = BE_DIMS[int(name[5]) - 1]
+            for k, ci in (("conv1", c_in), ("conv2", c_out)) + ((("downsample.0", c_in),) if c_out != c_in else ()):
+                w, b = get(f"{name}.{k}")
+                shape = (c_out, ci) + ((1, 1) if k == "downsample.0" else (3, 3))
+                if tuple(w.shape) != shape or b.numel() != c_out:
+                    raise ValueError(f"{name}.{k} must be weight {shape} and bias ({c_out}): got {tuple(w.shape)} and "
+                                     f"{tuple(b.shape)}")
+                names.append(f"{name}.{k}")
+            c_in = c_out
+        w, b = get("conv2")
+        if tuple(w.shape) != (BE_OUT[norm], BE_DIMS[2], 1, 1) or b.numel() != BE_OUT[norm]:
+            raise ValueError(f"conv2 must be weight ({BE_OUT[norm]}, {BE_DIMS[2]}, 1, 1) with norm = {norm!r}: got "
+                             f"{tuple(w.shape)}")
+        names.append("conv2")
+
+        def make():  # (one entry of the cache for the whole encoder)
+            convs = {}
+            for name in names[1:-1]:
+                if name.endswith("downsample.0"):
+                    continue
+                w, b = get(name)
+                w3, b3 = _pack_layout(w.detach().to(device, torch.float16),
+                                      b.detach().to(device, torch.float32).reshape(-1))
+                down = name.replace("conv1", "downsample.0")
+                if down != name and down in names:
+                    w1, b1 = _conv1x1_layout(*get(down), device)
+                    convs[name] = (w3, w1, torch.cat([b3, b1]), w.size(0), w.size(0))
+                else:
+                    convs[name] = (w3, None, b3, w.size(0), 0)
+            return cls(norm, _stem_layout(*get("conv1"), device), convs, _conv1x1_layout(*get("conv2"), device))
+        return _cached(tuple(t for k in names for t in get(k)), (device, "basic_encoder", norm), make)
+
+
+def be_sizes(H, W):
+    """The map sizes of the three levels: ((ceil(H / 2), ceil(W / 2)), (.. / 4), (.. / 8))"""
+    out = []
+    for _ in range(3):
+        H, W = (H + 1) // 2, (W + 1) // 2
+        out.append((H, W))
+    return tuple(out)
+
+
+def _be_check_size(norm, H, W):
+    h1, w1 = be_sizes(H, W)[0]
+    if H <= 0 or W <= 0 or h1 * w1 >= 1 << 20:
+        raise ValueError(f"images of {H} x {W}: the map of {h1} x {w1} must hold between 1 and 2^20 - 1 pixels")
+    h3, w3 = be_sizes(H, W)[2]
+    if norm == "instance" and h3 * w3 == 1:
+        raise ValueError(f"images of {H} x {W}: the last map is one pixel, which an instance norm cannot normalise "
+                         "(torch raises as well)")
+
+
+class BasicEncoderWorkspace:
+    """Every buffer a ``feature_encoder`` / ``context_encoder`` call on ``n``
+    images of ``H`` x ``W`` writes besides its result, so that a captured call has
+    stable addresses: the raw maps ``R0`` .. ``R12`` (``R5`` / ``Rd5`` and ``R9`` /
+    ``Rd9`` the halves of the stacked stride-2 launches' outputs), the block
+    outputs ``X0``, ``X1``, ``X3``, ``X5`` and, with ``norm="instance"``, the
+    statistics ``S0`` .. ``S12`` (float32 [n, C, 2]: mean, rstd) with the partial
+    sums they are merged from."""
+
+    def __init__(self, n, H, W, norm, device):
+        if norm not in BE_OUT:
+            raise ValueError(f"norm must be 'instance' or 'none': got {norm!r}")
+        _be_check_size(norm, H, W)
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        self.n, self.H, self.W, self.norm, self.device = n, H, W, norm, device
+        sizes = be_sizes(H, W)
+        half = lambda c, s: torch.empty(n, c, *s, dtype=torch.float16, device=self.device)  # noqa: E731
+        t = self.maps = {}
+        for k in range(13):
+            level = 0 if k < 5 else 1 if k < 9 else 2
+            t[f"R{k}"] = half(BE_DIMS[level] * (2 if k in (5, 9) else 1), sizes[level])
+        for k, level in ((0, 0), (1, 0), (3, 1), (5, 2)):
+            t[f"X{k}"] = half(BE_DIMS[level], sizes[level])
+        self.stats, self.part = {}, None
+        if norm == "instance":
+            L = _lib.load()
+            most = 0
+            for k in range(13):
+                rows, s = t[f"R{k}"].size(1), t[f"R{k}"].shape[2:]
+                self.stats[f"S{k}"] = torch.empty(n, rows, 2, dtype=torch.float32, device=self.device)
+                most = max(most, rows * L.wgsr_droid_be_parts(s[0], s[1], 2 if k in (5, 9) else 1))
+            self.part = torch.empty(n * most * 3, dtype=torch.float32, device=self.device)
+        # what the launches take of these buffers, looked up once: a source as (map, frame stride, statistics,
+        # frame stride), the output and the statistics launch (statistics, n, rows, partials) of each raw map
+        self.src, self.dst, self.fin = {}, {}, {}
+        for name, r in self.named().items():
+            if name[0] == "S":
+                continue
+            st = self.named().get("S" + name[1:]) if name[0] == "R" else None
+            self.src[name] = (r.data_ptr(), r.stride(0), _lib.ptr(st), st.stride(0) if st is not None else 0)
+        for name, r in t.items():
+            if name[0] == "R":
+                self.dst[name] = r.data_ptr()
+                if norm == "instance":
+                    parts = L.wgsr_droid_be_parts(r.size(2), r.size(3), 2 if name in ("R5", "R9") else 1)
+                    self.fin[name] = (self.stats["S" + name[1:]].data_ptr(), n, r.size(1), parts)
+
+    def named(self):
+        """name -> tensor: the raw maps (the stacked ones as their halves), block outputs and statistics; views"""
+        out = {}
+        for src, pre in ((self.maps, "R"), (self.stats, "S")):
+            for name, t in src.items():
+                if name in ("R5", "R9", "S5", "S9"):
+                    c = t.size(1) // 2
+                    out[name], out[f"{pre}d{name[1:]}"] = t[:, :c], t[:, c:]
+                else:
+                    out[name] = t
+        return out
+
+
+def _be_params(params, norm, dev):
+    if isinstance(params, BasicEncoder):
+        if params.norm != norm:
+            raise ValueError(f"params were packed with norm = {params.norm!r}; this call needs {norm!r}")
+        return params
+    name = "fnet." if norm == "instance" else "cnet."
+    prefix = name if f"{name}conv1.weight" in params else ""
+    return BasicEncoder.from_state_dict(params, prefix, norm, dev)
+
+
+def _be_run(who, norm, images, params, mean, std, out, workspace, return_intermediates):
+    _inference_only(who, images=images)
+    dev = droid_backends._device_of(images=images)
+    images = _activation("images", images, 3, dev, dtypes=tuple(droid_backends._DTYPE_TAG))
+    n, _, H, W = images.shape
+    _be_check_size(norm, H, W)
+    p = _be_params(params, norm, dev)
+    if p.stem[0].device != dev:
+        raise RuntimeError(f"params: expected tensors on {dev}, got {p.stem[0].device}")
+    if (mean is None) != (std is None):
+        raise ValueError("mean and std come together")
+    if mean is not None:
+        mean, std = (torch.as_tensor(v, dtype=torch.float32, device=dev).reshape(-1).contiguous() for v in (mean, std))
+        if mean.numel() != 3 or std.numel() != 3:
+            raise ValueError("mean and std must hold 3 values each")
+    ws = workspace
+    if ws is None:
+        ws = BasicEncoderWorkspace(n, H, W, norm, dev)
+    elif (ws.n, ws.H, ws.W, ws.norm, ws.device) != (n, H, W, norm, dev):
+        raise ValueError(f"workspace: made for {ws.n} images of {ws.H} x {ws.W}, norm {ws.norm!r}, on {ws.device}; "
+                         f"got {n} of {H} x {W}, {norm!r}, on {dev}")
+    sizes = be_sizes(H, W)
+    shape = (n, BE_DIMS[2]) + sizes[2]
+    if norm == "instance":
+        outs = (_out_buffer("out", out, shape, torch.float16, dev),)
+    else:
+        if out is not None and len(out) != 2:
+            raise ValueError("out must hold the two buffers (net, inp)")
+        outs = tuple(_out_buffer(k, out[i] if out else None, shape, torch.float16, dev) for i, k in
+                     enumerate(("net", "inp")))
+    if n == 0:
+        res = outs[0] if norm == "instance" else outs
+        return (res, ws.named()) if return_intermediates else res
+    L = _lib.load()
+    stream = _lib.stream_handle(dev)
+    inst = norm == "instance"
+    part = _lib.ptr(ws.part)
+    none = (None, 0, None, 0)
+    with torch.cuda.device(dev):
+        _lib.check(L.wgsr_droid_be_stem(images.data_ptr(), droid_backends._DTYPE_TAG[images.dtype], _lib.ptr(mean),
+                                        _lib.ptr(std), p.stem[0].data_ptr(), p.stem[1].data_ptr(), ws.dst["R0"], part,
+                                        n, H, W, stream))
+        if inst:
+            _lib.check(L.wgsr_droid_be_stats(part, *ws.fin["R0"], stream))
+        for name, main, second, side, c_in, stride, dst in BE_LAUNCHES:
+            hi, wi = sizes[BE_DIMS.index(c_in)]
+            _lib.check(L.wgsr_droid_be_conv(*ws.src[main], *(ws.src[second] if second else none),
+                                            ws.src[side][0] if side else None, c_in, stride, *p.args[name], 0,
+                                            ws.dst[dst], None, part, n, hi, wi, stream))
+            if inst:
+                _lib.check(L.wgsr_droid_be_stats(part, *ws.fin[dst], stream))
+        _lib.check(L.wgsr_droid_be_conv(*ws.src["R12"], *ws.src["X5"], None, BE_DIMS[2], 1, None, 0,
+                                        p.head[0].data_ptr(), p.out_dim, p.head[1].data_ptr(), 0 if inst else 1,
+                                        outs[0].data_ptr(), None if inst else outs[1].data_ptr(), None, n, *sizes[2],
+                                        stream))
+    res = outs[0] if inst else outs
+    return (res, ws.named()) if return_intermediates else res
+
+
+def feature_encoder(images, params, mean=None, std=None, out=None, workspace=None, return_intermediates=False):
+    """``DroidNet.fnet`` (droid_net.py:159; the ``BasicEncoder`` of extractor.py:
+    75-141 with an instance norm): ``images`` [n, 3, H, W] float32 or float16 (a
+    leading batch dimension of 1 is accepted and dropped) -> float16 [n, 128,
+    ceil(H / 8), ceil(W / 8)].  ``params``: a ``BasicEncoder`` or the
+    ``state_dict`` of ``DroidNet`` / of the module.  With ``mean`` / ``std`` (3
+    values each) the stem reads ``(images - mean) / std``, computed in float32
+    and rounded to float16 once, in place of ``inputs.sub_(MEAN).div_(STDV)``
+    (motion_filter.py:61-62).  14 convolution launches and, for the instance
+    norm, one small launch per raw map that merges its statistics; every
+    convolution writes its raw output once, and the norm, the ReLU and the
+    residual sum are applied as the next launch stages its tile (fp32, one
+    rounding), so that no launch only normalises, activates or adds.  No
+    allocation with ``workspace`` (a ``BasicEncoderWorkspace``) and ``out``, no
+    synchronisation, no host read: capturable in a graph.  Two runs give the same
+    bits, and an image's result does not depend on the others of the batch.
+    ``return_intermediates``: ``(out, {name: tensor})`` with the raw maps, block
+    outputs and statistics (``BasicEncoderWorkspace.named``)."""
+    return _be_run("feature_encoder", "instance", images, params, mean, std, out, workspace, return_intermediates)
+
+
+def context_encoder(images, params, mean=None, std=None, out=None, workspace=None, return_intermediates=False):
+    """``DroidNet.cnet`` with the split of motion_filter.py:42-43: ``(net, inp)
+    = (tanh(x[:, :128]), relu(x[:, 128:]))`` of the 256-row head, two float16 [n,
+    128, ceil(H / 8), ceil(W / 8)] tensors written by the head's launch.  As
+    ``feature_encoder`` without a norm: no statistics are computed or read.
+    ``out``: the pair of buffers."""
+    return _be_run("context_encoder", "none", images, params, mean, std, out, workspace, return_intermediates)

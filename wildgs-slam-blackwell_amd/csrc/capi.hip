@@ -24,7 +24,11 @@ thread_local char g_err[1024] = "";
 // Pinned host landing zone for the forward's pair counts + the event that
 // marks their arrival (one per host thread; never freed).
 struct HostCounters {
-  uint32_t* buf = nullptr;
+  uint32_t* buf = nullptr;  // kCounterBytes
+  // what the last copy into buf brought: the whole block (a copy queued ahead
+  // of the scan: the host reduces the slots) or the 64-byte header with the
+  // totals the scan's first wave left there (copy_counts_header)
+  bool whole = false;
   hipEvent_t ev = nullptr;
   // the D->H copy runs on a side stream behind `pre` (recorded after
   // k_preprocess), so the forward's stream goes straight on to the depth
@@ -33,9 +37,9 @@ struct HostCounters {
   // depth sort runs, which the copy then overlaps)
   hipStream_t side = nullptr;
   hipEvent_t pre = nullptr;
-  // per-bin default: k_publish_counts writes the block into `mbox` (coherent
-  // pinned memory, kCounterBytes) and then `seq` into mbox_seq; the host
-  // spins on that word instead of an event behind a blit-kernel copy (the
+  // per-bin default: the scan's first wave writes one record into `mbox`
+  // (coherent pinned memory), the sequence number in its first word; the host
+  // spins on that record instead of an event behind a blit-kernel copy (the
   // copy and its completion signal left the GPU idle ~6 us before the scan
   // and the host woke up later; measured in DESIGN.md section 8, round 6)
   uint4* mbox = nullptr;  // {seq << 8 | flags | 0x80 if > 32 bits, N_rect, N, N_bin}
@@ -67,11 +71,8 @@ BinningGuess& binning_guess() {
 
 // WGSR_PUBLISH_COUNTS=0: the blit-kernel copy + event wait for every forward
 bool publish_counts() {
-  static const bool on = [] {
-    const char* e = getenv("WGSR_PUBLISH_COUNTS");
-    return !(e && e[0] == '0');
-  }();
-  return on;
+  const char* e = getenv("WGSR_PUBLISH_COUNTS");  // (per call: tests compare the two paths)
+  return !(e && e[0] == '0');
 }
 
 HostCounters& host_counters() {
@@ -87,8 +88,7 @@ HostCounters& host_counters() {
     if (hc.side && hipEventCreateWithFlags(&hc.pre, hipEventDisableTiming) != hipSuccess) hc.pre = nullptr;
     if (!hc.pre) hc.side = nullptr;
     void* m = nullptr;
-    if (publish_counts() &&
-        hipHostMalloc(&m, 256, hipHostMallocCoherent | hipHostMallocMapped) == hipSuccess) {
+    if (hipHostMalloc(&m, 256, hipHostMallocCoherent | hipHostMallocMapped) == hipSuccess) {
       hc.mbox = static_cast<uint4*>(m);
       *hc.mbox = make_uint4(0u, 0u, 0u, 0u);
     }
@@ -354,27 +354,65 @@ int start_counts_readback(const Fwd& f, bool bin_depth, HostCounters& hc, Publis
   if (!hc.buf || !hc.ev) return set_error(WGSR_EHIP, "pinned counter buffer / event allocation failed");
   // (with the per-bin depth sort nothing would overlap the copy on the side
   // stream, whose start waits out an event round trip: copy in stream order)
-  // per-bin default: the scan's first wave publishes the counts (PublishJob)
-  if (bin_depth && hc.mbox) {
+  // the scan's first wave reduces the slots into the block's header whatever
+  // the schedule; per-bin default: it also publishes the counts (PublishJob)
+  *pub = PublishJob{f.counter, nullptr, 0u};
+  if (bin_depth && hc.mbox && publish_counts()) {
     // (no event behind it: an event record makes the runtime end the kernel
     // with a system-scope release, ~6 us before the next kernel starts; the
     // wait checks the stream itself instead)
     // (24-bit sequence numbers, never 0: the record's initial value)
-    *pub = PublishJob{f.counter, hc.mbox, hc.seq = (hc.seq % 0xFFFFFFu) + 1u};
-  } else if (hc.side && !bin_depth) {
+    pub->host = hc.mbox;
+    pub->seq = hc.seq = (hc.seq % 0xFFFFFFu) + 1u;
+  } else if (bin_depth) {
+    // WGSR_PUBLISH_COUNTS=0: the header, copied behind the scan (copy_counts_header)
+  } else if (hc.side) {
+    // (ahead of the depth sort and the scan, so the whole block: the host reduces the slots)
     HIPCHK(hipEventRecord(hc.pre, f.s));
     HIPCHK(hipStreamWaitEvent(hc.side, hc.pre, 0));
     HIPCHK(hipMemcpyAsync(hc.buf, f.counter, kCounterBytes, hipMemcpyDeviceToHost, hc.side));
     HIPCHK(hipEventRecord(hc.ev, hc.side));
+    hc.whole = true;
   } else {
     HIPCHK(hipMemcpyAsync(hc.buf, f.counter, kCounterBytes, hipMemcpyDeviceToHost, f.s));
     HIPCHK(hipEventRecord(hc.ev, f.s));
+    hc.whole = true;
   }
   return WGSR_OK;
 }
 
+// Behind the sort-bin scan: the block's header (the error flags and the
+// totals its first wave reduced from the slots) to pinned host memory.
+// record: hc.ev marks its arrival (wait_counts); else the caller synchronises the stream.
+int copy_counts_header(const Fwd& f, HostCounters& hc, bool record) {
+  HIPCHK(hipMemcpyAsync(hc.buf, f.counter, kCountHeaderBytes, hipMemcpyDeviceToHost, f.s));
+  if (record) HIPCHK(hipEventRecord(hc.ev, f.s));
+  else HIPCHK(hipStreamSynchronize(f.s));
+  hc.whole = false;
+  return WGSR_OK;
+}
+
+// the slots' totals from the host's copy of the block (whole) or of its header
+CountTotals host_count_totals(const HostCounters& hc) {
+  if (!hc.whole) {
+    CountTotals t;
+    memcpy(&t, hc.buf + kCountTotalsOffset / 4, sizeof t);
+    return t;
+  }
+  CountTotals t{0, 0, 0, 0, 0};
+  const CountSlot* slots = count_slots(hc.buf);
+  for (int i = 0; i < kCountSlots; ++i) {
+    t.rect += slots[i].rect;
+    t.list += slots[i].list;
+    t.bin += slots[i].bin;
+    t.key_hi = slots[i].key_hi > t.key_hi ? slots[i].key_hi : t.key_hi;
+    t.key_nlo = slots[i].key_nlo > t.key_nlo ? slots[i].key_nlo : t.key_nlo;
+  }
+  return t;
+}
+
 int wait_counts(const Fwd& f, HostCounters& hc, const PublishJob& pub, Counts* c) {
-  if (!pub.counter) {  // a copy is on its way
+  if (!pub.host) {  // a copy is on its way
     HIPCHK(hipEventSynchronize(hc.ev));
   } else {
     uint4 rec = make_uint4(0u, 0u, 0u, 0u);
@@ -408,33 +446,22 @@ int wait_counts(const Fwd& f, HostCounters& hc, const PublishJob& pub, Counts* c
       *c = Counts{rec.y, rec.z, rec.w, rec.x & 0x7Fu, true};
       return WGSR_OK;
     }
-    // not published, or a count beyond 32 bits: the block itself
-    HIPCHK(hipMemcpyAsync(hc.buf, f.counter, kCounterBytes, hipMemcpyDeviceToHost, f.s));
-    HIPCHK(hipStreamSynchronize(f.s));
+    // not published, or a count beyond 32 bits: the block's header (the publishing wave wrote it)
+    if (int e = copy_counts_header(f, hc, false)) return e;
   }
-  *c = Counts{0, 0, 0, hc.buf[1], false};
-  const uint64_t* partial = reinterpret_cast<const uint64_t*>(hc.buf + 4);
-  for (int i = 0; i < kRectPairLanes; ++i) {
-    c->N_rect += partial[i];
-    c->N += partial[kRectPairLanes + i];
-    c->N_bin += partial[2 * kRectPairLanes + i];
-  }
+  const CountTotals t = host_count_totals(hc);
+  *c = Counts{(size_t)t.rect, (size_t)t.list, (size_t)t.bin, hc.buf[1], false};
   return WGSR_OK;
 }
 
 // After wait_counts: the maxima of the visible depth keys and of their complements.  (The
 // published counts carry no key range: the bins-too-full switch reads the block, rarely.)
 int read_depth_range(const Fwd& f, HostCounters& hc, const Counts& c, uint32_t* hi, uint32_t* nlo) {
-  if (c.published) {
-    HIPCHK(hipMemcpyAsync(hc.buf, f.counter, kCounterBytes, hipMemcpyDeviceToHost, f.s));
-    HIPCHK(hipStreamSynchronize(f.s));
-  }
-  const uint32_t* rw = hc.buf + kDepthRangeOffset / 4;
-  *hi = *nlo = 0;
-  for (int i = 0; i < kRectPairLanes; ++i) {
-    *hi = rw[i] > *hi ? rw[i] : *hi;
-    *nlo = rw[kRectPairLanes + i] > *nlo ? rw[kRectPairLanes + i] : *nlo;
-  }
+  if (c.published)
+    if (int e = copy_counts_header(f, hc, false)) return e;
+  const CountTotals t = host_count_totals(hc);
+  *hi = t.key_hi;
+  *nlo = t.key_nlo;
   return WGSR_OK;
 }
 
@@ -477,7 +504,7 @@ int queue_depth_sort(const Fwd& f, bool full, bool zero_sup, const uint32_t** de
   }
   if (zero_sup)
     HIPCHK(hipMemsetAsync(hist + depth_sort_sup_offset_words(P), 0, 4 * depth_sort_sup_words(P), f.s));
-  STAGE(f.a, f.s, launch_depth_sort(dkey, dkey_alt, dval, dval_alt, P, f.counter + kDepthRangeOffset / 4,
+  STAGE(f.a, f.s, launch_depth_sort(dkey, dkey_alt, dval, dval_alt, P, count_slots(f.counter),
                                     f.counter + 2, hist, f.s));
   *depth_order = dval_alt;
   return WGSR_OK;
@@ -699,7 +726,7 @@ int wgsr_rasterize_forward(const wgsr_raster_args* args, wgsr_alloc_fn geom_allo
   } sync_on_error{s};
   { StageTimer T(kStPreprocess, s);
   const hipError_t pe = launch_preprocess(a, f.geom, radii, n_touched, f.counter + 1,
-                                          reinterpret_cast<unsigned long long*>(f.counter + 4), f.bshift,
+                                          count_slots(f.counter), f.bshift,
                                           preprocess_zero_job(f, dc, sched), s, f.im<uint32_t>(f.IL.meta));
   if (pe == hipSuccess && dc) dc->parity ^= 1;  // k_preprocess, which zeroes the other block, is queued
   sync_on_error.armed = true;
@@ -712,6 +739,8 @@ int wgsr_rasterize_forward(const wgsr_raster_args* args, wgsr_alloc_fn geom_allo
   if (sched != DepthSched::kBins)
     if (int e = queue_depth_sort(f, sched == DepthSched::kFull, false, &depth_order)) return e;
   if (int e = queue_scan(f, depth_order, pub)) return e;
+  if (sched == DepthSched::kBins && !pub.host)
+    if (int e = copy_counts_header(f, hc, true)) return e;
   // the predicted binning buffer, allocated while the GPU works
   BinningGuess& bg = binning_guess();
   void* binning = nullptr;
@@ -831,11 +860,11 @@ int wgsr_rasterize_forward_cap(const wgsr_raster_args* args, int64_t cap, wgsr_a
   const ZeroJob zj = preprocess_zero_job(f, nullptr, DepthSched::kBins);  // (the dual scan's superblock sums)
   { StageTimer T(kStPreprocess, s);
   STAGE(a, s, launch_preprocess(a, f.geom, radii, n_touched, f.counter + 1,
-                                reinterpret_cast<unsigned long long*>(f.counter + 4), f.bshift, zj, s, meta)); }
-  STAGE(a, s, launch_cap_counts(reinterpret_cast<const unsigned long long*>(f.counter + 4), (uint64_t)C, (uint64_t)C,
+                                count_slots(f.counter), f.bshift, zj, s, meta)); }
+  STAGE(a, s, launch_cap_counts(count_slots(f.counter), (uint64_t)C, (uint64_t)C,
                                 counts, meta, s));
   // block sums of (list length, bins) in index order
-  if (int e = queue_scan(f, nullptr, PublishJob{})) return e;
+  if (int e = queue_scan(f, nullptr, PublishJob{f.counter, nullptr, 0u})) return e;  // (the totals into the header)
   g_depth_order_off = -1;
   // the bin sort reads its key count from counts[4] and hands back the bin bounds
   return queue_lists_and_render(f, binning, plan, nullptr, true, C, counts + 4);

@@ -163,16 +163,15 @@ __device__ __forceinline__ uint3 preprocess_one(
 
 // A preprocess wave's pair counts (upstream's num_rendered, exact pairs, bin
 // pairs) and visible depth-key range into the counter block: one atomic per
-// wave each, spread over kRectPairLanes words.  The wave sums / maxima are
+// wave each, all five into the wave's own 64-byte record (CountSlot, one
+// memory-side segment).  The wave sums / maxima are
 // DPP row reductions + four readlanes (SGPR results, no LDS round trips);
 // per-lane rect areas of 2^26 or more (images beyond ~17 Gpixel) take the
-// 64-bit shuffle path.
+// 64-bit shuffle path.  (1M / 1080p / SH3: k_preprocess2 98.3-99.0 -> 78.5-79.6
+// us against five arrays of 64 words, where 8 or 16 slots shared a segment.)
 __device__ __forceinline__ void wave_pair_counts(const uint3 ac, uint32_t khi, uint32_t knlo,
-                                                 unsigned long long* __restrict__ rect_pairs,
-                                                 unsigned long long* __restrict__ list_pairs,
-                                                 unsigned long long* __restrict__ bin_pairs,
-                                                 uint32_t* __restrict__ drange) {
-  const uint32_t slot = blockIdx.x % kRectPairLanes;
+                                                 CountSlot* __restrict__ slots) {
+  CountSlot* __restrict__ rec = slots + blockIdx.x % kCountSlots;
   unsigned long long area, cnt, nbin;
   if (wave_any(ac.x >= (1u << 26))) {
     area = ac.x;
@@ -191,12 +190,12 @@ __device__ __forceinline__ void wave_pair_counts(const uint3 ac, uint32_t khi, u
   }
   const uint32_t kh = wave_maximum_u32(khi), kn = wave_maximum_u32(knlo);
   if (threadIdx.x % 64 == 0) {
-    atomicAdd(&rect_pairs[slot], area);
-    atomicAdd(&list_pairs[slot], cnt);
-    atomicAdd(&bin_pairs[slot], nbin);
+    atomicAdd(&rec->rect, area);
+    atomicAdd(&rec->list, cnt);
+    atomicAdd(&rec->bin, nbin);
     // the depth sort's key range (DepthKeyPlan): max key, max complement
-    if (kh) atomicMax(&drange[slot], kh);
-    if (kn) atomicMax(&drange[kRectPairLanes + slot], kn);
+    if (kh) atomicMax(&rec->key_hi, kh);
+    if (kn) atomicMax(&rec->key_nlo, kn);
   }
 }
 
@@ -258,10 +257,8 @@ __global__ __launch_bounds__(kPreWave) void k_preprocess2(
     int H, float tanx, float tany, int gx, int gy, int prefiltered, float4* __restrict__ splat,
     ListRec* __restrict__ lrec, uint32_t* __restrict__ clamped,
     uint32_t* __restrict__ dkey, int32_t* __restrict__ radii, int32_t* __restrict__ n_touched,
-    uint32_t* __restrict__ err_flag, unsigned long long* __restrict__ rect_pairs,
-    unsigned long long* __restrict__ list_pairs, unsigned long long* __restrict__ bin_pairs, int bshift,
-    uint32_t* __restrict__ tb, uint8_t* __restrict__ gflag, uint32_t* __restrict__ drange, const ZeroJob zero,
-    uint32_t* __restrict__ meta) {
+    uint32_t* __restrict__ err_flag, CountSlot* __restrict__ slots, int bshift,
+    uint32_t* __restrict__ tb, uint8_t* __restrict__ gflag, const ZeroJob zero, uint32_t* __restrict__ meta) {
   extern __shared__ float s_sh[];  // nch x 64 x kCh floats (chunk-major)
   const int lane = threadIdx.x;
   const int i0 = blockIdx.x * kPreWave, i = i0 + lane;
@@ -334,7 +331,7 @@ __global__ __launch_bounds__(kPreWave) void k_preprocess2(
       clamped[i] = cbits;
     }
   }
-  wave_pair_counts(ac, khi, knlo, rect_pairs, list_pairs, bin_pairs, drange);
+  wave_pair_counts(ac, khi, knlo, slots);
   zero_share(zero, blockIdx.x, gridDim.x, lane, kPreWave);
   if (blockIdx.x == 0 && lane == 0) {
     meta[1] = 0u;  // no capacity overflow (ImageLayout::meta)
@@ -354,22 +351,17 @@ __global__ __launch_bounds__(256) void k_mark_visible(int P, const float* __rest
 }  // namespace
 
 // Capacity-mode forward: the counter block's partial pair counts (upstream's
-// rect pairs, exact pairs, bin pairs: kRectPairLanes u64 each) -> counts[0..2]
+// rect pairs, exact pairs, bin pairs of the kCountSlots records) -> counts[0..2]
 // (saturating u32), the bin-pair count clamped to the buffers (counts[4], what
 // the sort reads as its key count) and the overflow flag (counts[3] and the
 // image buffer's meta[1], which makes the render backward a no-op).
 
-__global__ __launch_bounds__(64) void k_cap_counts(const unsigned long long* __restrict__ partial,
+__global__ __launch_bounds__(64) void k_cap_counts(const CountSlot* __restrict__ slots,
                                                    uint64_t cap_rect, uint64_t cap_bin, uint32_t* __restrict__ counts,
                                                    uint32_t* __restrict__ meta) {
   const int t = threadIdx.x;
-  unsigned long long r = partial[t], e = partial[kRectPairLanes + t], b = partial[2 * kRectPairLanes + t];
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    r += __shfl_xor(r, off, 64);
-    e += __shfl_xor(e, off, 64);
-    b += __shfl_xor(b, off, 64);
-  }
+  const CountTotals tot = count_slots_reduce(slots, t);
+  const unsigned long long r = tot.rect, e = tot.list, b = tot.bin;
   if (t == 0) {
     const uint32_t ovf = (r > cap_rect || b > cap_bin) ? 1u : 0u;
     counts[0] = (uint32_t)min(r, 0xFFFFFFFFull);
@@ -380,20 +372,16 @@ __global__ __launch_bounds__(64) void k_cap_counts(const unsigned long long* __r
     meta[1] = ovf;
   }
 }
-static_assert(kRectPairLanes == 64, "k_cap_counts: one lane per partial");
 
-hipError_t launch_cap_counts(const unsigned long long* partial, uint64_t cap_rect, uint64_t cap_bin, uint32_t* counts,
+hipError_t launch_cap_counts(const CountSlot* slots, uint64_t cap_rect, uint64_t cap_bin, uint32_t* counts,
                              uint32_t* meta, hipStream_t s) {
-  hipLaunchKernelGGL(k_cap_counts, dim3(1), dim3(64), 0, s, partial, cap_rect, cap_bin, counts, meta);
+  hipLaunchKernelGGL(k_cap_counts, dim3(1), dim3(64), 0, s, slots, cap_rect, cap_bin, counts, meta);
   return hipGetLastError();
 }
 
 hipError_t launch_preprocess(const wgsr_raster_args& a, void* geom, int32_t* radii, int32_t* n_touched,
-                             uint32_t* err_flag, unsigned long long* rect_pairs, int bshift, const ZeroJob& zero,
+                             uint32_t* err_flag, CountSlot* slots, int bshift, const ZeroJob& zero,
                              hipStream_t s, uint32_t* meta) {
-  unsigned long long* list_pairs = rect_pairs + kRectPairLanes;
-  unsigned long long* bin_pairs = rect_pairs + 2 * kRectPairLanes;
-  uint32_t* drange = reinterpret_cast<uint32_t*>(rect_pairs + 3 * kRectPairLanes);  // kDepthRangeOffset
   if (a.P == 0) return hipSuccess;
   const GeomLayout L(a.P);
   const int gx = (a.W + kTile - 1) / kTile, gy = (a.H + kTile - 1) / kTile;
@@ -412,9 +400,8 @@ hipError_t launch_preprocess(const wgsr_raster_args& a, void* geom, int32_t* rad
                      lds2, s, a.P, a.D, a.M, a.means3D, a.scales, a.rotations, a.opacities, a.shs, a.colors,
                      a.cov3D_precomp, a.scale_modifier, a.viewmatrix, a.projmatrix, a.campos, a.W, a.H, a.tan_fovx,
                      a.tan_fovy, gx, gy, a.prefiltered, at<float4>(geom, L.splat), at<ListRec>(geom, L.lrec),
-                     at<uint32_t>(geom, L.clamped), at<uint32_t>(geom, L.dkey), radii, n_touched, err_flag, rect_pairs,
-                     list_pairs, bin_pairs, bshift, at<uint32_t>(geom, L.tb), at<uint8_t>(geom, L.gflag), drange, zero,
-                     meta);
+                     at<uint32_t>(geom, L.clamped), at<uint32_t>(geom, L.dkey), radii, n_touched, err_flag, slots,
+                     bshift, at<uint32_t>(geom, L.tb), at<uint8_t>(geom, L.gflag), zero, meta);
   return hipGetLastError();
 }
 

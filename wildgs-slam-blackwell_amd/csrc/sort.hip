@@ -462,13 +462,13 @@ __global__ __launch_bounds__(NT) void k_radix_scatter_wide(
 // Same reduce-then-scan structure as the 8-bit passes (superblock sums, no
 // row-scan launch), with up to 1024 digits: thread t owns digits
 // [t dpt, t dpt + dpt), dpt = ceil(digits / 256).
-static_assert(kRectPairLanes == 64, "one range word per lane");
 __device__ __forceinline__ int bitlen32(uint32_t x) {
   return x ? 32 - __clz((int)x) : 0;
 }
-// The range words: one per lane, max-reduced across the wave.  Every kernel
-// issues its key loads (and the scatter its first digit-sum loads) before it
-// needs the plan, so this adds no round trip of its own.
+// The range words: kCountSlots / 64 slots per lane, max-reduced across the
+// wave.  Every kernel issues its key loads (and the scatter its first
+// digit-sum loads) before it needs the plan, so this adds no round trip of
+// its own.
 // wave max into a scalar: DPP within each 16-lane row (shifted-in lanes
 // read 0), then the four rows' lane 15 by readlane
 __device__ __forceinline__ uint32_t wave_max_u32_uniform(uint32_t x) {
@@ -480,14 +480,22 @@ __device__ __forceinline__ uint32_t wave_max_u32_uniform(uint32_t x) {
   const uint32_t c = (uint32_t)__builtin_amdgcn_readlane((int)x, 47), d = (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
   return max(max(a, b), max(c, d));
 }
-// The first kernel (pass 0's histogram) reduces k_preprocess's 2 x 64 range
-// words and its workgroup 0 leaves the result in two words (the counter
-// block's pad words) that every later kernel reads with one scalar load,
-// whose wait does not hold up the vector loads issued before the plan is
-// needed.
-__device__ __forceinline__ uint2 depth_range_reduce(const uint32_t* __restrict__ range) {
+// The first kernel (pass 0's histogram) reduces the key maxima of
+// k_preprocess's count slots and its workgroup 0 leaves the result in two
+// words (the counter block's pad words) that every later kernel reads with
+// one scalar load, whose wait does not hold up the vector loads issued before
+// the plan is needed.
+static_assert(kCountSlots % 64 == 0, "depth_range_reduce: whole rounds of 64 lanes");
+__device__ __forceinline__ uint2 depth_range_reduce(const CountSlot* __restrict__ range) {
   const int lane = threadIdx.x & 63;
-  return make_uint2(wave_max_u32_uniform(range[lane]), wave_max_u32_uniform(range[kRectPairLanes + lane]));
+  constexpr int R = kCountSlots / 64;
+  uint2 k[R];  // (every load issued before the first max)
+#pragma unroll
+  for (int r = 0; r < R; ++r) k[r] = *reinterpret_cast<const uint2*>(&range[64 * r + lane].key_hi);
+  uint2 m = k[0];
+#pragma unroll
+  for (int r = 1; r < R; ++r) m = make_uint2(max(m.x, k[r].x), max(m.y, k[r].y));
+  return make_uint2(wave_max_u32_uniform(m.x), wave_max_u32_uniform(m.y));
 }
 __device__ __forceinline__ DepthKeyPlan depth_plan_from2(const uint32_t* __restrict__ range2) {
   return depth_key_plan(range2[0], ~range2[1]);
@@ -495,7 +503,7 @@ __device__ __forceinline__ DepthKeyPlan depth_plan_from2(const uint32_t* __restr
 
 template <int I, int PASS>
 __global__ __launch_bounds__(256) void k_depth_hist(const uint32_t* __restrict__ keys, uint32_t n,
-                                                    const uint32_t* __restrict__ range, uint32_t* __restrict__ range2,
+                                                    const CountSlot* __restrict__ range, uint32_t* __restrict__ range2,
                                                     uint32_t* __restrict__ hist, uint32_t* __restrict__ sup) {
   __shared__ uint32_t s_h[kDepthMaxDigits];
   const int t = threadIdx.x;
@@ -925,7 +933,7 @@ hipError_t radix_sort_pairs(uint32_t* keys, uint32_t* keys_alt, uint32_t* vals, 
 
 template <int I>
 static hipError_t depth_sort_tiled(uint32_t* keys, uint32_t* keys_alt, uint32_t* vals, uint32_t* vals_alt, size_t n,
-                                   const uint32_t* range, uint32_t* range2, uint32_t* scratch, hipStream_t s) {
+                                   const CountSlot* range, uint32_t* range2, uint32_t* scratch, hipStream_t s) {
   const uint32_t nb = (uint32_t)((n + 256 * I - 1) / (256 * I)), nsup = (nb + kSupBlocks - 1) / kSupBlocks;
   uint32_t* hist = scratch;
   uint32_t* sup = scratch + depth_sort_sup_offset_words(n);
@@ -946,7 +954,7 @@ static hipError_t depth_sort_tiled(uint32_t* keys, uint32_t* keys_alt, uint32_t*
 }
 
 hipError_t launch_depth_sort(uint32_t* keys, uint32_t* keys_alt, uint32_t* vals, uint32_t* vals_alt, size_t n,
-                             const uint32_t* range, uint32_t* range2, uint32_t* scratch, hipStream_t s) {
+                             const CountSlot* range, uint32_t* range2, uint32_t* scratch, hipStream_t s) {
   if (n == 0) return hipSuccess;
   if (n > (size_t)kStCount) return hipErrorInvalidValue;
   switch (sort_items(n)) {

@@ -743,47 +743,101 @@ __host__ __device__ inline uint32_t sort_blocks(size_t n) {
   const size_t tile = 256 * (size_t)sort_items(n);
   return (uint32_t)((n + tile - 1) / tile);
 }
-// upstream num_rendered is accumulated in this many u64 partial sums (spread
-// so that the per-wave atomics of k_preprocess do not serialise on one word)
-constexpr int kRectPairLanes = 64;
-// geometry counter block: u32 [0] scan total, [1] error flags, [2..3] the depth
-// sort's reduced key range (launch_depth_sort),
-// then u64 rect-pair partials [kRectPairLanes], u64 listed-pair partials
-// [kRectPairLanes], u64 bin-pair partials [kRectPairLanes], then u32 maxima
-// of the visible Gaussians' depth keys [kRectPairLanes] and of their
-// complements [kRectPairLanes] (the depth sort's key range, DepthKeyPlan)
-constexpr size_t kDepthRangeOffset = 16 + 3 * 8 * kRectPairLanes;
-constexpr size_t kCounterBytes = kDepthRangeOffset + 2 * 4 * kRectPairLanes;
+// k_preprocess's waves add their pair counts and depth-key maxima into one
+// of this many records (slot = workgroup % kCountSlots), one 64-byte record
+// per slot: the atomics execute at the memory side as 64-byte requests, so a
+// wave's five land in one segment and a segment serves 5 x waves / kCountSlots
+// of them (the earlier five arrays of 64 words put 8 u64 or 16 u32 slots in a
+// segment: 1 953 and 3 906 requests per segment at 1M Gaussians).
+constexpr int kCountSlots = 256;
+struct alignas(64) CountSlot {
+  unsigned long long rect, list, bin;  // upstream's num_rendered (rect areas), exact list pairs, bin pairs
+  uint32_t key_hi, key_nlo;            // maxima of the visible depth keys and of their complements (DepthKeyPlan)
+  uint32_t pad[8];
+};
+static_assert(sizeof(CountSlot) == 64, "one 64-byte segment per slot");
+// the slots' reduction: what the scan's first wave leaves in the header
+struct CountTotals {
+  unsigned long long rect, list, bin;
+  uint32_t key_hi, key_nlo;
+};
+// geometry counter block, a 64-byte header followed by the slots: u32 [0]
+// scan total, [1] error flags, [2..3] the depth sort's reduced key range
+// (launch_depth_sort); bytes [16, 48) the slots' CountTotals (publish_counts);
+// then CountSlot [kCountSlots]
+constexpr size_t kCountTotalsOffset = 16;
+constexpr size_t kCountHeaderBytes = 64;
+constexpr size_t kCountSlotsOffset = kCountHeaderBytes;
+constexpr size_t kCounterBytes = kCountSlotsOffset + sizeof(CountSlot) * kCountSlots;
+static_assert(kCountTotalsOffset + sizeof(CountTotals) <= kCountHeaderBytes, "the totals fit the header");
+__host__ __device__ inline CountSlot* count_slots(uint32_t* counter) {
+  return reinterpret_cast<CountSlot*>(counter + kCountSlotsOffset / 4);
+}
+__host__ __device__ inline const CountSlot* count_slots(const uint32_t* counter) {
+  return reinterpret_cast<const CountSlot*>(counter + kCountSlotsOffset / 4);
+}
+
+// A wave's reduction of the slots: lane l reads slots l, l + 64, ... (two
+// 16-byte loads each, every load issued before the first use: one memory
+// round trip), then the wave sums / maxima.  Every lane returns the totals.
+static_assert(kCountSlots % 64 == 0, "count_slots_reduce: whole rounds of 64 lanes");
+__device__ __forceinline__ CountTotals count_slots_reduce(const CountSlot* __restrict__ slots, int lane) {
+  constexpr int R = kCountSlots / 64;
+  uint4 a[R], b[R];  // (rect, list) and (bin, key_hi, key_nlo)
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    const uint4* p = reinterpret_cast<const uint4*>(slots + 64 * r + lane);
+    a[r] = p[0];
+    b[r] = p[1];
+  }
+  unsigned long long v[3] = {0ull, 0ull, 0ull};
+  uint32_t hi = 0u, nlo = 0u;
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    v[0] += (unsigned long long)a[r].x | ((unsigned long long)a[r].y << 32);
+    v[1] += (unsigned long long)a[r].z | ((unsigned long long)a[r].w << 32);
+    v[2] += (unsigned long long)b[r].x | ((unsigned long long)b[r].y << 32);
+    hi = max(hi, b[r].z);
+    nlo = max(nlo, b[r].w);
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) v[k] += (unsigned long long)__shfl_xor((long long)v[k], off, 64);
+    hi = max(hi, (uint32_t)__shfl_xor((int)hi, off, 64));
+    nlo = max(nlo, (uint32_t)__shfl_xor((int)nlo, off, 64));
+  }
+  return CountTotals{v[0], v[1], v[2], hi, nlo};
+}
 
 // The forward's one host wait without a copy-engine round trip: the first
-// wave of the scan that follows k_preprocess sums the counter block's three
-// sets of 64 u64 partials (upstream's num_rendered, the exact list pairs, the
-// bin pairs) and lane 0 writes ONE aligned 16-byte record into fine-grained
-// (coherent) pinned host memory: {seq << 8 | error flags | 0x80 if a count
-// needs more than 32 bits, N_rect, N, N_bin}.  One store carries the sequence
-// number and the counts together, so no fence orders them (a system-scope
-// release would write the whole L2 back); the host polls the record.
+// wave of the scan that follows k_preprocess reduces the counter block's
+// slots (upstream's num_rendered, the exact list pairs, the bin pairs, the
+// key range), lane 0 leaves the CountTotals in the block's header (what the
+// host's copy paths read) and, with a mailbox, writes ONE aligned 16-byte
+// record into fine-grained (coherent) pinned host memory: {seq << 8 | error
+// flags | 0x80 if a count needs more than 32 bits, N_rect, N, N_bin}.  One
+// store carries the sequence number and the counts together, so no fence
+// orders them (a system-scope release would write the whole L2 back); the
+// host polls the record.
 struct PublishJob {
-  const uint32_t* counter = nullptr;  // null: no publish
-  uint4* host = nullptr;
+  uint32_t* counter = nullptr;  // null: no reduction
+  uint4* host = nullptr;        // null: the header only
   uint32_t seq = 0;
 };
 __device__ __forceinline__ void publish_counts(const PublishJob& pj, int lane) {
-  const unsigned long long* partial = reinterpret_cast<const unsigned long long*>(pj.counter + 4);
-  unsigned long long v[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    v[k] = partial[k * kRectPairLanes + lane];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v[k] += (unsigned long long)__shfl_xor((long long)v[k], off, 64);
-  }
+  const CountTotals t = count_slots_reduce(count_slots(pj.counter), lane);
   if (lane == 0) {
-    const bool big = ((v[0] | v[1] | v[2]) >> 32) != 0;
-    *pj.host = make_uint4((pj.seq << 8) | (pj.counter[1] & 0x7Fu) | (big ? 0x80u : 0u), (uint32_t)v[0],
-                          (uint32_t)v[1], (uint32_t)v[2]);
+    uint4* h = reinterpret_cast<uint4*>(pj.counter + kCountTotalsOffset / 4);
+    h[0] = make_uint4((uint32_t)t.rect, (uint32_t)(t.rect >> 32), (uint32_t)t.list, (uint32_t)(t.list >> 32));
+    h[1] = make_uint4((uint32_t)t.bin, (uint32_t)(t.bin >> 32), t.key_hi, t.key_nlo);
+    if (pj.host) {
+      const bool big = ((t.rect | t.list | t.bin) >> 32) != 0;
+      *pj.host = make_uint4((pj.seq << 8) | (pj.counter[1] & 0x7Fu) | (big ? 0x80u : 0u), (uint32_t)t.rect,
+                            (uint32_t)t.list, (uint32_t)t.bin);
+    }
   }
 }
-static_assert(kRectPairLanes == 64, "publish_counts: one lane per partial");
 
 // ---- depth sort over the visible key range -------------------------------------
 // Depth keys are the float bits of view-space depth (> 0.2 for a visible
@@ -926,7 +980,7 @@ struct GeomLayout {
     totals = take(kSortTotalsBytes);
     bsum = take(8 * ((P + kPackedScanTile - 1) / kPackedScanTile + 1));  // uint2 block sums of the (dual) scans
     bsup = take(8 * kScanSupStride * (packed_scan_supers(P) + 1));  // uint2 sums of kScanSupBlocks block sums
-    counter = take(kCounterBytes);  // see kCounterBytes
+    counter = take(kCounterBytes);  // header + count slots, see kCounterBytes
     gflag = take(P);               // per Gaussian: some tile's backward wrote a partial record
                                    // (zeroed by k_preprocess, set by the render backward)
     total = o;

@@ -33,14 +33,14 @@ hipError_t radix_sort_pairs(uint32_t* keys, uint32_t* keys_alt, uint32_t* vals, 
 size_t sort_sup_words(size_t n, int begin_bit, int end_bit, size_t* offset_words);
 
 // Depth sort (DepthKeyPlan): three stable passes over key'' of the depth keys
-// in `keys` (values = input positions); range = the counter block's range
-// words (kDepthRangeOffset), range2 = two words for their reduction, scratch = depth_sort_status_bytes(n) bytes whose
+// in `keys` (values = input positions); range = the counter block's count
+// slots (their key maxima), range2 = two words for their reduction, scratch = depth_sort_status_bytes(n) bytes whose
 // superblock sums (depth_sort_sup_offset_words / depth_sort_sup_words) are
 // zero.  Result: rank -> position in vals_alt; keys_alt holds key'' when the
 // plan leaves extra_bits (the caller's fix-up pass sorts those), else
 // garbage.  keys and vals are clobbered.
 hipError_t launch_depth_sort(uint32_t* keys, uint32_t* keys_alt, uint32_t* vals, uint32_t* vals_alt, size_t n,
-                             const uint32_t* range, uint32_t* range2, uint32_t* scratch, hipStream_t s);
+                             const CountSlot* range, uint32_t* range2, uint32_t* scratch, hipStream_t s);
 
 // out[i] = sum_{j<i} vals[idx ? idx[j] : j]  (i in [0, n]; out has n + 1
 // entries), optional scatter_out[idx[i]] = out[i]; *total_out = out[n].
@@ -63,15 +63,16 @@ int num_bits(uint32_t n);  // bits needed to represent values in [0, n)
 int set_error(int code, const char* fmt, ...);
 
 // ---- preprocess (raster_pre.hip) --------------------------------------------
-// rect_pairs[0..kRectPairLanes) += upstream's num_rendered contributions (rect
-// areas); rect_pairs[kRectPairLanes..2 kRectPairLanes) += exact list lengths
-// rect_pairs[2 kRectPairLanes..3 kRectPairLanes) += bins touched (bshift > 0;
-// geometry tb[g] = exact list length | bins touched << 16)
+// slots (the counter block's kCountSlots records, zero before the call): rect
+// += upstream's num_rendered contributions (rect areas), list += exact list
+// lengths, bin += bins touched (bshift > 0; geometry tb[g] = exact list
+// length | bins touched << 16), key_hi / key_nlo = maxima of the visible
+// depth keys and of their complements
 hipError_t launch_preprocess(const wgsr_raster_args& a, void* geom, int32_t* radii, int32_t* n_touched,
-                             uint32_t* err_flag, unsigned long long* rect_pairs, int bshift, const ZeroJob& zero, hipStream_t s, uint32_t* meta);
-// capacity-mode forward: counter partials -> counts [N_rect, N_exact, N_bin,
+                             uint32_t* err_flag, CountSlot* slots, int bshift, const ZeroJob& zero, hipStream_t s, uint32_t* meta);
+// capacity-mode forward: the count slots -> counts [N_rect, N_exact, N_bin,
 // overflow, clamped N_bin] and the overflow flag into meta[1]
-hipError_t launch_cap_counts(const unsigned long long* partial, uint64_t cap_rect, uint64_t cap_bin, uint32_t* counts,
+hipError_t launch_cap_counts(const CountSlot* slots, uint64_t cap_rect, uint64_t cap_bin, uint32_t* counts,
                              uint32_t* meta, hipStream_t s);
 // present[i] = Gaussian i lies beyond the near plane of `view` (wgsr_mark_visible)
 hipError_t launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t s);

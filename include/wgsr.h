@@ -1236,6 +1236,56 @@ int wgsr_droid_be_conv(const void* r, int64_t r_frame, const float* r_stats, int
                        int epilogue, void* out, void* out2, float* part, int n, int hi, int wi, void* stream);
 int wgsr_droid_be_stats(const float* part, float* stats, int n, int rows, int parts, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * wgsr.frontend.filter_mono_depth (csrc/droid_mono_filter.hip): the tracker's
+ * DINO-consistency filter of the metric depth prior,
+ * DepthVideo.filter_high_err_mono_depth (depth_video.py:281-349).
+ *
+ * poses [num, 7], disps_up [num, H, W] fp32 (the metric disparities at full
+ * resolution), mask_up [num, H, W] bytes (bool; row idx is updated in place:
+ * bytes are only ever cleared), intrinsics [4] = (fx, fy, cx, cy) at 1/8 scale
+ * (multiplied by 8 inside), jj [n_ref] the reference frames (device int64; a
+ * frame named twice counts twice).  feats: the DINO maps [frames, hd, wd, C]
+ * fp32, 16-byte aligned, C a multiple of 4 -- with feats_packed == 0 the whole
+ * buffer, frame f at row f (frames >= num); with feats_packed != 0 n_ref + 1
+ * rows: the keyframe's, then those of jj[0], jj[1], ...
+ *
+ * For each reference k and each pixel (x, y) of frame j = jj[k]: X0 = ((x -
+ * cx) / fx, (y - cy) / fy, 1), D = disps_up[j, y, x], X1 = R X0 + t D with (R,
+ * t) = pose[idx] pose[j]^-1; Z < 0.1 is replaced by 1; u = fx X / Z + cx, v =
+ * fy Y / Z + cy, d = D / Z; the target is (round(u), round(v)), half to even,
+ * valid inside the image with d > 0 (compared as floats).  The candidate is
+ * matched when the cosine between frame j's feature at (x, y) and frame idx's
+ * at the target -- both sampled as F.interpolate(mode='bilinear',
+ * align_corners=False) from hd x wd to H x W samples them, norms max(|.|,
+ * 1e-12) -- exceeds sim_thresh.  Among the matched candidates of one (k,
+ * target) the largest source index y W + x wins; with w its d, err = |1 / w - 1
+ * / disps_up[idx, target]| w (a zero disparity: inf) adds one to accurate
+ * [target] when err < err_thresh, else to inaccurate[target].  mask_up[idx] is
+ * cleared where accurate <= 1, inaccurate > 0 and disps_up[idx] > 0.
+ * accurate / inaccurate: [H, W] int32, written when non-null.
+ *
+ * No full-resolution feature map is formed: the cosines are combinations of
+ * entries of the cell Gram matrices F_j F_idx^T and F F^T (fp32 MFMA), held in
+ * workspace with one 64-bit winner word per (k, target).  workspace: caller-
+ * owned device scratch of wgsr_droid_mono_filter_workspace_bytes (-1, and
+ * wgsr_last_error, for sizes the call would refuse), 16-byte aligned.
+ * Launches only: no allocation, no synchronisation, no host read, no memset
+ * node -- capturable in a HIP graph; the winner is chosen by an integer
+ * atomic max, so two runs give the same bits.  n_ref == 0 writes zero counts
+ * and leaves the mask as it is.  status (one device word, written by every
+ * call): 0, or WGSR_MONO_FILTER_BAD_JJ when an entry of jj lies outside [0,
+ * num) -- the call then writes neither the mask nor the counts.  Bad sizes,
+ * idx outside [0, num), null pointers or a short workspace: WGSR_EINVAL before
+ * any launch. */
+#define WGSR_MONO_FILTER_BAD_JJ 1u
+int64_t wgsr_droid_mono_filter_workspace_bytes(int n_ref, int H, int W, int hd, int wd);
+int wgsr_droid_mono_filter(const float* poses, const float* disps_up, uint8_t* mask_up, const float* intrinsics,
+                           const float* feats, int feats_packed, const int64_t* jj, int n_ref, int idx, int num,
+                           int H, int W, int hd, int wd, int C, float sim_thresh, float err_thresh,
+                           int32_t* accurate, int32_t* inaccurate, void* workspace, int64_t workspace_bytes,
+                           uint32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

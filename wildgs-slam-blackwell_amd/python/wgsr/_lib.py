@@ -368,6 +368,12 @@ def load():
                                          + [_fp] * 3 + [c_int] * 3 + [_fp])
         L.wgsr_droid_be_stats.restype = c_int
         L.wgsr_droid_be_stats.argtypes = [_fp, _fp, c_int, c_int, c_int, _fp]
+        # wgsr.frontend.filter_mono_depth (csrc/droid_mono_filter.hip)
+        L.wgsr_droid_mono_filter_workspace_bytes.restype = ctypes.c_int64
+        L.wgsr_droid_mono_filter_workspace_bytes.argtypes = [c_int] * 5
+        L.wgsr_droid_mono_filter.restype = c_int
+        L.wgsr_droid_mono_filter.argtypes = ([_fp] * 5 + [c_int, _fp] + [c_int] * 8 + [ctypes.c_float] * 2
+                                             + [_fp] * 3 + [ctypes.c_int64, _fp, _fp])
         L.wgsr_last_error.restype = ctypes.c_char_p
         L.wgsr_last_error.argtypes = []
         L.wgsr_version.restype = ctypes.c_char_p
@@ -418,6 +424,7 @@ EXPORTED_SYMBOLS = (
     "wgsr_droid_conv3x3_relu", "wgsr_droid_update_heads", "wgsr_droid_graph_agg",
     "wgsr_droid_gru", "wgsr_droid_corr_encoder", "wgsr_droid_flow_encoder",
     "wgsr_droid_be_parts", "wgsr_droid_be_stem", "wgsr_droid_be_conv", "wgsr_droid_be_stats",
+    "wgsr_droid_mono_filter_workspace_bytes", "wgsr_droid_mono_filter",
 )
 
 VIEW_RECORD_FLOATS = 12   # WGSR_VIEW_RECORD_FLOATS

@@ -47,6 +47,11 @@
                         launches that write each raw map once and apply the
                         norm, the ReLU and the residual sum as the next launch
                         stages its tile (csrc/droid_basic_encoder.hip)
+* ``filter_mono_depth`` DepthVideo.filter_high_err_mono_depth (depth_video.py:
+                        281-349): the DINO-consistency filter of the metric
+                        depth prior from fp32 MFMA Gram matrices of the cell
+                        maps, no full-resolution feature map
+                        (csrc/droid_mono_filter.hip)
 
 poses [num, 7] = (tx, ty, tz, qx, qy, qz, qw), world to camera; disps
 [num, ht, wd]; intrinsics [4] = (fx, fy, cx, cy); device fp32 tensors.
@@ -1729,3 +1734,145 @@ def context_encoder(images, params, mean=None, std=None, out=None, workspace=Non
     ``feature_encoder`` without a norm: no statistics are computed or read.
     ``out``: the pair of buffers."""
     return _be_run("context_encoder", "none", images, params, mean, std, out, workspace, return_intermediates)
+
+
+# ---------------------------------------------------------------------------
+# The DINO-consistency filter of the metric depth prior (csrc/droid_mono_filter.hip)
+# ---------------------------------------------------------------------------
+DINO_PATCH = 14  # the DINO maps are [H // 14, W // 14, C]
+MONO_FILTER_STATUS = {1: "an entry of jj is outside [0, N) (WGSR_MONO_FILTER_BAD_JJ)"}
+
+
+def mono_filter_workspace_bytes(n_ref, H, W):
+    """Bytes of device scratch ``filter_mono_depth`` needs for ``n_ref`` reference
+    frames of H x W pixels: the winner words and the Gram matrices."""
+    nbytes = _lib.load().wgsr_droid_mono_filter_workspace_bytes(n_ref, H, W, H // DINO_PATCH, W // DINO_PATCH)
+    if nbytes < 0:
+        _lib.check(1)  # WGSR_EINVAL: raises with the library's message for the refused sizes
+    return nbytes
+
+
+def filter_mono_depth(poses, mono_disps_up, mono_mask_up, intrinsics, dino_feats, idx, jj, sim_thresh=0.9,
+                      err_thresh=0.02, return_counts=False, check=True, workspace=None):
+    """``DepthVideo.filter_high_err_mono_depth`` (depth_video.py:281-349) on the
+    video buffers: clears the pixels of ``mono_mask_up[idx]`` whose metric depth
+    disagrees with the depth reprojected from the frames ``jj``, a reprojected
+    pixel counting only where the DINO features of the two pixels match.
+
+    ``poses`` [N, 7], ``mono_disps_up`` [N, H, W] float32 and ``mono_mask_up``
+    [N, H, W] bool (row ``idx`` is updated in place) on the device;
+    ``intrinsics``: frame 0's (fx, fy, cx, cy) at 1/8 scale, multiplied by
+    ``down_scale`` = 8 inside as the reference does; ``dino_feats`` [N, H // 14,
+    W // 14, C] float32 on any device -- the reference keeps them on the host,
+    and they may stay there: the rows ``idx`` and ``jj`` are then copied over,
+    about 1.5 MB a frame; ``jj`` the 1-D list of reference frames, which the
+    caller takes from the graph as ``graph.jj[graph.ii == idx]``.  (The
+    reference's loop that would pad ``jj`` up to
+    ``nb_ref_frame_metric_depth_filtering`` frames discards the result of its
+    ``torch.cat``: it does nothing, and nothing is padded here.)
+
+    For each j of ``jj`` and each pixel (x, y) of frame j: the point ((x - cx) /
+    fx, (y - cy) / fy, 1) with disparity D = ``mono_disps_up[j, y, x]`` goes
+    through pose[idx] pose[j]^-1; a depth Z < 0.1 is replaced by 1 (the
+    reference's ``proj``); the target is the projection rounded half to even,
+    valid inside the image with d = D / Z > 0.  The candidate is matched when
+    the cosine of frame j's DINO feature at (x, y) and frame idx's at the target,
+    both sampled bilinearly (``align_corners=False``) from the cell maps,
+    exceeds ``sim_thresh``.  Among the matched candidates of one (j, target) the
+    one with the largest source index y W + x wins -- what the reference's
+    scatter yields in order on one CPU thread, and here the defined rule where
+    the reference's ``index_put`` is nondeterministic on a GPU.  With w the
+    winner's d, ``|1 / w - 1 / mono_disps_up[idx, target]| w < err_thresh``
+    (a zero disparity: inf) adds one to the target's accurate count, else to
+    its inaccurate count: once per (j, target).  The mask is cleared where
+    accurate <= 1, inaccurate > 0 and the disparity of idx is positive.  An
+    empty ``jj`` changes nothing; a j listed twice counts twice.
+
+    No full-resolution feature map is formed: the cosines are 16 + 20 entries of
+    the cell Gram matrices (fp32 MFMA), exact up to the order of the fp32 sums.
+    Four launches, no host read with the features on the device and
+    ``check=False``: the call can be captured in a graph (``jj`` then has to be a
+    device tensor already), and two calls give the same bits.  ``check`` reads
+    the kernel's status word back and raises ``RuntimeError`` for an entry of
+    ``jj`` outside [0, N) (nothing was written); ``idx`` is always checked.
+    ``return_counts``: ``(accurate, inaccurate)``, int32 [H, W].  ``workspace``: a
+    uint8 device tensor of at least ``mono_filter_workspace_bytes(len(jj), H, W)``
+    bytes to use as scratch, e.g. one buffer the tracker keeps across keyframes;
+    without it the scratch is allocated per call."""
+    who = "filter_mono_depth"
+    _inference_only(who, poses=poses, mono_disps_up=mono_disps_up, dino_feats=dino_feats)
+    if poses.dim() != 2 or poses.size(1) != 7 or poses.dtype != torch.float32:
+        raise RuntimeError("poses must be a float32 tensor of dimensions (N, 7)")
+    if mono_disps_up.dim() != 3 or mono_disps_up.dtype != torch.float32:
+        raise RuntimeError("mono_disps_up must be a float32 tensor of dimensions (N, H, W)")
+    if mono_mask_up.dtype != torch.bool or mono_mask_up.shape != mono_disps_up.shape:
+        raise RuntimeError(f"mono_mask_up must be a bool tensor of mono_disps_up's dimensions "
+                           f"{tuple(mono_disps_up.shape)}: got {mono_mask_up.dtype} {tuple(mono_mask_up.shape)}")
+    H, W = mono_disps_up.size(1), mono_disps_up.size(2)
+    hd, wd = H // DINO_PATCH, W // DINO_PATCH
+    if dino_feats.dim() != 4 or dino_feats.dtype != torch.float32:
+        raise RuntimeError("dino_feats must be a float32 tensor of dimensions (N, H // 14, W // 14, C)")
+    if hd < 1 or wd < 1 or tuple(dino_feats.shape[1:3]) != (hd, wd):
+        raise ValueError(f"dino_feats must be (N, {hd}, {wd}, C) for frames of {H} x {W}: got "
+                         f"{tuple(dino_feats.shape)}")
+    C = dino_feats.size(3)
+    if C == 0 or C % 4 != 0:
+        raise ValueError(f"dino_feats: the channel count C = {C} must be a positive multiple of 4")
+    intrinsics = torch.as_tensor(intrinsics)
+    if intrinsics.numel() != 4:
+        raise RuntimeError("intrinsics must have 4 elements (fx, fy, cx, cy)")
+    jj = torch.as_tensor(jj)
+    if jj.numel() == 0:  # (an empty list comes out as a float tensor)
+        jj = jj.to(torch.int64)
+    if jj.dim() != 1 or jj.dtype.is_floating_point or jj.dtype == torch.bool:
+        raise RuntimeError("jj must be a 1-D tensor (or list) of frame indices")
+    N = min(poses.size(0), mono_disps_up.size(0), dino_feats.size(0))
+    idx = int(idx)
+    if not 0 <= idx < N:
+        raise RuntimeError(f"idx = {idx} must index frames [0, {N})")
+    droid_backends._contiguous(poses=poses, mono_disps_up=mono_disps_up, mono_mask_up=mono_mask_up)
+    dev = droid_backends._device_of(poses=poses, mono_disps_up=mono_disps_up, mono_mask_up=mono_mask_up)
+    packed = dino_feats.device != dev
+    if packed and dino_feats.device.type == "cuda":
+        raise RuntimeError(f"dino_feats: expected a tensor on {dev} or on the host, got {dino_feats.device}")
+    if packed or (check and jj.device.type == "cpu"):
+        # the features are gathered by jj on the host (or jj is there already): bounded here
+        jj_host = jj.to("cpu", torch.int64)
+        if jj_host.numel() and (int(jj_host.min()) < 0 or int(jj_host.max()) >= N):
+            raise RuntimeError(f"{who}: jj must index frames [0, {N}): got values in [{int(jj_host.min())}, "
+                               f"{int(jj_host.max())}]; nothing was written")
+    E = jj.numel()
+    counts = None
+    if return_counts:  # (every element is written by the call)
+        make = torch.empty if E else torch.zeros
+        counts = (make(H, W, dtype=torch.int32, device=dev), make(H, W, dtype=torch.int32, device=dev))
+    if E == 0:
+        return counts
+    if packed:
+        rows = torch.cat([torch.tensor([idx], dtype=torch.int64), jj_host])
+        feats = dino_feats.detach()[rows].to(dev).contiguous()
+    else:
+        feats = dino_feats.detach()
+        droid_backends._contiguous(dino_feats=feats)
+    jj = jj.to(dev, torch.int64).contiguous()
+    intrinsics = intrinsics.detach().to(dev, torch.float32).reshape(-1).contiguous()
+    L = _lib.load()
+    nbytes = mono_filter_workspace_bytes(E, H, W)
+    if workspace is None:
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    elif (workspace.dtype != torch.uint8 or workspace.device != dev or not workspace.is_contiguous()
+          or workspace.numel() < nbytes or workspace.data_ptr() % 16):
+        raise RuntimeError(f"workspace must be a contiguous, 16-byte aligned uint8 tensor of at least {nbytes} bytes "
+                           f"on {dev} (mono_filter_workspace_bytes)")
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.wgsr_droid_mono_filter(poses.data_ptr(), mono_disps_up.data_ptr(), mono_mask_up.data_ptr(),
+                                            intrinsics.data_ptr(), feats.data_ptr(), int(packed), jj.data_ptr(), E, idx,
+                                            N, H, W, hd, wd, C, float(sim_thresh), float(err_thresh),
+                                            _lib.ptr(counts[0]) if counts else None,
+                                            _lib.ptr(counts[1]) if counts else None, workspace.data_ptr(),
+                                            workspace.numel(),
+                                            status.data_ptr(), _lib.stream_handle(dev)))
+    if check:
+        _raise_status(who, status, MONO_FILTER_STATUS)
+    return counts
